@@ -12,9 +12,18 @@ all inputs already resident in HBM.  With N > 1 every rank aligns its own batch
 (weak scaling; utterances are independent, reference core.pyx:44-45) and the int32
 duration vectors are all-gathered over RCCL in buckets on a side stream.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description) with two
-extra objects: `roofline` (dominant kernel, timed with HIP events on the launch
-stream) and `cpu_baseline` (the reference / its C restatement on the host cores).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (one timed step) and the configuration.  A plain run sets up, warms up,
+times exactly K steps and prints that line, nothing more.  `--full` adds everything
+else the benchmark measures and checks, after the timed region: repeats of the region
+and the one-batch-at-a-time figure, guards on the timed outputs and the reference's
+hashes, `roofline` (dominant kernel, timed with HIP events on the launch stream) and
+`cpu_baseline` (the reference / its C restatement on the host cores).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the arrays
+a caller receives -- as DIR/<name>.npy (float32; a fixed, seeded sample where an array
+would take the whole 64 MB budget).  The inputs are seeded: the same arguments give the
+same inputs in every run, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -39,6 +48,30 @@ CONTIGUOUS_LOGP = False          # --contiguous-logp: the step's intermediate in
 SUSTAINED_STEPS = 20000          # the long region reported beside a short timed one (`sustained`), and the default K
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 SIM_KERNEL = "softattn_rt_kernel"     # the similarity kernel configs[1] launches (csrc/softattn.hip: the row-tile form)
+# --steps / --warmup when not given, per --config
+DEFAULT_STEPS = {"c2": (SUSTAINED_STEPS, 2000), "c3": (1000, 100), "c4": (500, 50), "c5": (1000, 100)}
+DUMP_BUDGET = 64 * 10 ** 6       # --dump-outputs: bytes of array data at most
+DUMP_SAMPLE = 1 << 20            # elements of the fixed sample that stands for an array too large for the budget
+
+
+def dump_outputs(dirname: str, arrays: dict, sample=()) -> None:
+    """--dump-outputs: every tensor of `arrays` as dirname/<name>.npy, float32 (float64 stays float64; integer and bf16 values
+    are exact in float32).  For the names in `sample`: the elements at DUMP_SAMPLE fixed flat indices (a seeded permutation,
+    ascending), the same in every run.  Called right after the timed region, before anything else touches the buffers."""
+    os.makedirs(dirname, exist_ok=True)
+    out, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach().contiguous()                 # (a pitched intermediate: its logical [B,Tx,Ty] elements)
+        if name in sample:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += a.nbytes
+        out[name] = a
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than the {DUMP_BUDGET} allowed")
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 class Step:
@@ -366,27 +399,30 @@ def run_c4(args, world: int, rank: int, local: int):
     for _ in range(args.warmup):
         step()
     elapsed = timed(args.steps)
-    # this rank's DP time alone (HIP events), for the load-balance line
-    t_dp = event_time_us(lambda: _lib.check(lib.aligner_maxpath_forward_f32(
-        value.data_ptr(), None, 0, t_x.data_ptr(), t_y.data_ptr(), None, dur.data_ptr(), ws.data_ptr(), ws.numel(),
-        cap, TXM, TYM, -1e9, 0, torch.cuda.current_stream(dev).cuda_stream)), 10, dev)
-    dp_all = [t_dp]
-    if dist is not None:
-        t = torch.zeros(world, dtype=torch.float64, device=dev)
-        t[rank] = t_dp
-        dist.all_reduce(t)
-        dp_all = [float(x) for x in t.cpu()]
-    # parity on the timed output: per contiguous 64-utterance shard, the reference's duration hashes
-    ok = None
-    try:
-        with open(os.path.join(ROOT, "tests", "golden", "appendix_a.json")) as f:
-            rec = json.load(f)
-        fh = full.cpu().numpy().astype(np.int32)
-        ok = all(hashlib.sha256(np.ascontiguousarray(fh[64 * s:64 * s + 64]).tobytes()).hexdigest() ==
-                 rec[f"C4-shard{s}"]["dur_sha256"] for s in range(8))
-    except (OSError, KeyError, ValueError):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"durations": full})      # the whole job's durations, in utterance order
+    if args.full:
+        # this rank's DP time alone (HIP events), for the load-balance line
+        t_dp = event_time_us(lambda: _lib.check(lib.aligner_maxpath_forward_f32(
+            value.data_ptr(), None, 0, t_x.data_ptr(), t_y.data_ptr(), None, dur.data_ptr(), ws.data_ptr(), ws.numel(),
+            cap, TXM, TYM, -1e9, 0, torch.cuda.current_stream(dev).cuda_stream)), 10, dev)
+        dp_all = [t_dp]
+        if dist is not None:
+            t = torch.zeros(world, dtype=torch.float64, device=dev)
+            t[rank] = t_dp
+            dist.all_reduce(t)
+            dp_all = [float(x) for x in t.cpu()]
+        # parity on the timed output: per contiguous 64-utterance shard, the reference's duration hashes
         ok = None
-    assert ok is not False, "gathered durations differ from the reference's hashes"
+        try:
+            with open(os.path.join(ROOT, "tests", "golden", "appendix_a.json")) as f:
+                rec = json.load(f)
+            fh = full.cpu().numpy().astype(np.int32)
+            ok = all(hashlib.sha256(np.ascontiguousarray(fh[64 * s:64 * s + 64]).tobytes()).hexdigest() ==
+                     rec[f"C4-shard{s}"]["dur_sha256"] for s in range(8))
+        except (OSError, KeyError, ValueError):
+            ok = None
+        assert ok is not False, "gathered durations differ from the reference's hashes"
     if rank == 0:
         ups = N_UTT * args.steps / elapsed
         out = {
@@ -398,10 +434,11 @@ def run_c4(args, world: int, rank: int, local: int):
             "config": {"workload": "configs[3]: 512 variable-length utterances [<=400 tokens, <=2000 frames] fp32, DP "
                                    "durations per rank + one RCCL all_gather of int32 durations per pass",
                        "utterances": N_UTT, "per_rank": cap, "parallelism": f"LPT batch shards x{max(world, 1)}"},
-            "load_balance": {"dp_cost_max_over_mean": round(max(loads) / (sum(loads) / len(loads)), 4),
-                             "dp_kernel_us_per_rank": [round(x, 1) for x in dp_all]},
-            "durations_match_reference_hashes": ok,
         }
+        if args.full:
+            out["load_balance"] = {"dp_cost_max_over_mean": round(max(loads) / (sum(loads) / len(loads)), 4),
+                                   "dp_kernel_us_per_rank": [round(x, 1) for x in dp_all]}
+            out["durations_match_reference_hashes"] = ok
         _emit(out)
     if dist is not None:
         dist.barrier()
@@ -474,6 +511,24 @@ def run_c3(args, world: int):
         step()
     elapsed = _timed_region(step, args.steps, dev)
     res, logp = out["res"], out["logp"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"path": res.path, "durations": res.durations, "tokens": res.tok, "logp": logp},
+                     sample=("logp",))
+    ups = Bc * args.steps / elapsed
+    line = {
+        "metric": "aligned utterances/sec, full OTA pipeline (conv encoders -> similarity -> alignment search), "
+                  "[B=64, 512-dim text x 200, 80-mel x 900]",
+        "value": round(ups, 1), "unit": "utterances/s", "frames_per_s": round(ups * Ty, 1), "n_gpus": 1,
+        "steps": args.steps, "warmup": max(args.warmup, 3), "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "configs[2]: conv text encoder (512->1024 k3, ReLU, 1024->80 k1) + conv mel encoder (80->160 k3, "
+                               "160->80, 80->80) + similarity (L2, C=80) + log-softmax + monotonic alignment search with dense "
+                               "fp32 path and int32 durations; [64, 512x200 text embedding, 80x900 mel], eager launches",
+                   "batch_per_gpu": Bc, "t_text": Tx, "t_mel": Ty},
+    }
+    if not args.full:
+        _emit(line)
+        return
     # guards on the timed outputs: every log-prob column is a distribution over the text, the path is one token per
     # frame, monotone, and its row sums are the durations
     col = torch.logsumexp(logp, dim=1)
@@ -505,25 +560,13 @@ def run_c3(args, world: int):
     }
     dom = "text encoder conv 512->1024 k3 alone (split pass + conv_gemm_kernel, fp32 out)"     # the step's dominant launch pair
     tfl = stages[dom][1] / (stages[dom][0] * 1e-6) / 1e12
-    ups = Bc * args.steps / elapsed
-    line = {
-        "metric": "aligned utterances/sec, full OTA pipeline (conv encoders -> similarity -> alignment search), "
-                  "[B=64, 512-dim text x 200, 80-mel x 900]",
-        "value": round(ups, 1), "unit": "utterances/s", "frames_per_s": round(ups * Ty, 1), "n_gpus": 1,
-        "steps": args.steps, "warmup": max(args.warmup, 3), "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "configs[2]: conv text encoder (512->1024 k3, ReLU, 1024->80 k1) + conv mel encoder (80->160 k3, "
-                               "160->80, 80->80) + similarity (L2, C=80) + log-softmax + monotonic alignment search with dense "
-                               "fp32 path and int32 durations; [64, 512x200 text embedding, 80x900 mel], eager launches",
-                   "batch_per_gpu": Bc, "t_text": Tx, "t_mel": Ty},
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(tfl, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(tfl / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None, "kernel_us": round(stages[dom][0], 2),
-                     "algorithmic_flops": stages[dom][1],
-                     "note": "algorithmic flops of the fp32 convolution; the kernel issues three bf16 MFMAs per product "
-                             "(hi*hi + hi*lo + lo*hi of the split operands), i.e. 3x these flops on the matrix cores",
-                     "all_stages_us": {n: round(v[0], 2) for n, v in stages.items()},
-                     "not_in_the_step_us": {n: round(v, 2) for n, v in beside.items()}},
-    }
+    line["roofline"] = {"bound": "mfma", "kernel": dom, "achieved": round(tfl, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(tfl / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None, "kernel_us": round(stages[dom][0], 2),
+                        "algorithmic_flops": stages[dom][1],
+                        "note": "algorithmic flops of the fp32 convolution; the kernel issues three bf16 MFMAs per product "
+                                "(hi*hi + hi*lo + lo*hi of the split operands), i.e. 3x these flops on the matrix cores",
+                        "all_stages_us": {n: round(v[0], 2) for n, v in stages.items()},
+                        "not_in_the_step_us": {n: round(v, 2) for n, v in beside.items()}}
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = _cpu_dp_baseline(logp.contiguous().cpu().numpy(), np.full(Bc, Tx, np.int32), np.full(Bc, Ty, np.int32),
                                                 "this step's own [64,200,900] log-probs")
@@ -558,6 +601,25 @@ def run_c5(args, world: int):
         step()
     elapsed = _timed_region(step, args.steps, dev)
     lp, res, bs = out["lp"], out["res"], out["bs"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"path": res.path, "durations": res.durations, "boundary_search_boundaries": bs.boundaries,
+                                         "boundary_search_durations": bs.durations, "boundary_search_map_score": bs.map_score,
+                                         "logp": lp}, sample=("path", "logp"))
+    ups = Bc * args.steps / elapsed
+    line = {
+        "metric": "aligned utterances/sec, long-form [B=8, T_text=500, T_mel=4000]: bf16 similarity + alignment search (int32 "
+                  "path) + MoBoAligner boundary search",
+        "value": round(ups, 1), "unit": "utterances/s", "frames_per_s": round(ups * Ty, 1), "n_gpus": 1,
+        "steps": args.steps, "warmup": max(args.warmup, 3), "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16 scores, f32 arithmetic, i32 path",
+        "data": "synthetic",
+        "config": {"workload": f"configs[4]: similarity (L2, C=80) with bf16 log-probs -> maximum_path on them (dense int32 path + "
+                               f"durations) -> boundary search with max duration {D} on the same energies; [8,500,4000], eager launches",
+                   "batch_per_gpu": Bc, "t_text": Tx, "t_mel": Ty, "max_duration": D},
+    }
+    if not args.full:
+        _emit(line)
+        return
     assert aligner_amd.read_status(dev) == 0 and mobo.read_status(dev) == 0
     # guards on the timed outputs
     assert int(res.durations.sum()) == Bc * Ty and bool((res.path.sum(1) == 1).all())
@@ -599,27 +661,15 @@ def run_c5(args, world: int):
     }
     dom = max(stages, key=lambda n: stages[n][0])
     gbs = stages[dom][1] / (stages[dom][0] * 1e-6) / 1e9
-    ups = Bc * args.steps / elapsed
-    line = {
-        "metric": "aligned utterances/sec, long-form [B=8, T_text=500, T_mel=4000]: bf16 similarity + alignment search (int32 "
-                  "path) + MoBoAligner boundary search",
-        "value": round(ups, 1), "unit": "utterances/s", "frames_per_s": round(ups * Ty, 1), "n_gpus": 1,
-        "steps": args.steps, "warmup": max(args.warmup, 3), "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16 scores, f32 arithmetic, i32 path",
-        "data": "synthetic",
-        "config": {"workload": f"configs[4]: similarity (L2, C=80) with bf16 log-probs -> maximum_path on them (dense int32 path + "
-                               f"durations) -> boundary search with max duration {D} on the same energies; [8,500,4000], eager launches",
-                   "batch_per_gpu": Bc, "t_text": Tx, "t_mel": Ty, "max_duration": D},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None, "kernel_us": round(stages[dom][0], 2),
-                     "algorithmic_bytes": stages[dom][1],
-                     "note": "boundary search bytes: energies read twice (2+2 B/cell: normalisers, chain), normalisers written and "
-                             "read (4+4), durations written (2); it is bound by the dependent chain over the 500 token rows "
-                             "(DESIGN 7.1), not by memory",
-                     "all_stages_us": {n: round(v[0], 2) for n, v in stages.items()},
-                     "not_in_the_step_us": training_extra},
-        "alignment_path_matches_reference_hash_on_C5_scores": ref_ok,
-    }
+    line["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None, "kernel_us": round(stages[dom][0], 2),
+                        "algorithmic_bytes": stages[dom][1],
+                        "note": "boundary search bytes: energies read twice (2+2 B/cell: normalisers, chain), normalisers written and "
+                                "read (4+4), durations written (2); it is bound by the dependent chain over the 500 token rows "
+                                "(DESIGN 7.1), not by memory",
+                        "all_stages_us": {n: round(v[0], 2) for n, v in stages.items()},
+                        "not_in_the_step_us": training_extra}
+    line["alignment_path_matches_reference_hash_on_C5_scores"] = ref_ok
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = _cpu_dp_baseline(synth.synth_value(Bc, Tx, Ty, 5, bits=8, denom=8.0), np.full(Bc, Tx, np.int32),
                                                 np.full(Bc, Ty, np.int32), "the [8,500,4000] scores of SURVEY Appendix A")
@@ -686,9 +736,16 @@ def _self_launch(n: int) -> None:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=SUSTAINED_STEPS,
-                    help="timed steps (default: a region long enough for the GPU's clocks and caches to have settled: ~0.6 s)")
-    ap.add_argument("--warmup", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: a region long enough for the GPU's clocks and caches to have settled: ~0.6 s "
+                         "-- c2 20 000, c3 / c5 1 000, c4 500)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: c2 2 000, c3 / c5 100, c4 50)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, everything beside the headline figure: repeats of the region and the "
+                         "one-batch-at-a-time figure, guards on the timed outputs and the reference's hashes, per-kernel times "
+                         "and `roofline`, `cpu_baseline` (the --no-* options below thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, 64 MB at most)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a captured HIP graph")
     ap.add_argument("--gather-every", type=int, default=96,
                     help="steps per duration all-gather bucket (N>1): few, large collectives -- an all_gather every 18 steps "
@@ -720,6 +777,11 @@ def main():
     args = ap.parse_args()
     global CONTIGUOUS_LOGP
     CONTIGUOUS_LOGP = bool(args.contiguous_logp)
+    d_steps, d_warmup = DEFAULT_STEPS[args.config]
+    args.steps = d_steps if args.steps is None else args.steps
+    args.warmup = d_warmup if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started by hand (or by a driver that does not wrap it in torch.distributed.run): start
@@ -731,15 +793,13 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.config in ("c3", "c5"):
-        if args.steps == SUSTAINED_STEPS and args.warmup == 2000:
-            args.steps, args.warmup = 1000, 100          # a step is 0.2-0.6 ms of several launches: ~0.5 s (30 steps: 227-233 us at
-                                                         # configs[2], the clocks still settling; 3 000: 211 us)
+        # (default: 1 000 steps -- a step is 0.2-0.6 ms of several launches: ~0.5 s (30 steps: 227-233 us at configs[2], the
+        # clocks still settling; 3 000: 211 us))
         return run_c3(args, world) if args.config == "c3" else run_c5(args, world)
     if args.config == "c4":
         if world != args.gpus:
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run")
-        if args.steps == SUSTAINED_STEPS and args.warmup == 2000:
-            args.steps, args.warmup = 500, 50            # a pass is ~0.1-1 ms: keep the default run short
+        # (default: 500 steps -- a pass is ~0.1-1 ms: keep the default run short)
         return run_c4(args, world, rank, local)
     dist = None
     # ALIGNER_BENCH_FORCE_DIST=1: take the multi-rank code path (RCCL group, duration buckets) with one rank
@@ -856,6 +916,50 @@ def main():
 
     run(args.warmup)
     elapsed = timed(args.steps)                    # the reported figure: one region of exactly K steps
+    if args.dump_outputs and rank == 0:
+        # the region's last step: the buffers of the stream it ran on; N>1: its durations are in its slot of a gather bucket
+        last = args.steps - 1
+        st = steps[last % nstreams]
+        outs = {"path": st.path, "tokens": st.tok, "durations": st.dur}
+        if dist is not None:
+            bi, slot = (last // ge) % 2, last % ge
+            outs["durations"] = buckets[bi][slot]
+            outs["durations_gathered"] = gathered[bi][slot::ge]           # [world, B, TX]: every rank's last step
+        dump_outputs(args.dump_outputs, outs)
+    n = max(world, 1)
+    ups = n * B * args.steps / elapsed
+    out = {
+        "metric": "aligned utterances/sec + frames/sec, [B=64,T_text=200,T_mel=1000]",
+        "value": round(ups, 1), "unit": "utterances/s", "frames_per_s": round(ups * TY, 1),
+        "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "configs[1]: similarity (L2, C=80) + monotonic alignment search, "
+                               "[B=64,T_text=200,T_mel=1000] fp32 per GPU, dense fp32 path + int32 durations out",
+                   "batch_per_gpu": B, "t_text": TX, "t_mel": TY, "c_att": C_ATT,
+                   "launch": "hipGraph" if step.graph is not None else "eager",
+                   "batches_in_flight": nstreams,
+                   "intermediate": ("log-probs [B,Tx,Ty] contiguous (--contiguous-logp)" if CONTIGUOUS_LOGP else
+                                    f"log-probs [B,Tx,Ty] at a row pitch of {step.ld} elements (rows on whole 128-byte lines: "
+                                    "aligner_softattn_ld -> aligner_maxpath_ld); inputs and outputs contiguous"),
+                   "path_stores": ("non-temporal (ALIGNER_F_STREAM_PATH) with the batches in flight, ordinary in the "
+                                   "serial figure" if stream_path else "ordinary"),
+                   "dense_path": {"batches_in_flight": args.path_mode, "serial": args.serial_path_mode,
+                                  "note": "fused = aligner_maxpath: one launch, zero workgroups on the idle CUs beside the search, "
+                                          "the utterances' workgroups write the ones; inline = zeros on a second graph branch beside the similarity kernel, the search "
+                                          "kernel writes the ones (ALIGNER_F_PATH_PREZEROED); branch = zeros beside the "
+                                          "search, then a scatter kernel; expand = one kernel behind the search"},
+                   "parallelism": f"batch-sharded x{n}" + (f", RCCL all_gather of durations every "
+                                                           f"{ge} steps" if n > 1 else "")},
+    }
+    if not args.full:
+        if rank == 0:
+            _emit(out)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # spread of that figure: the same region four more times (not part of `value`)
     extra = [timed(args.steps) for _ in range(4)] if args.repeats else []
     # ... and, where the reported region is short, one long one: a region of a few hundred steps is over within ~10 ms of the
@@ -936,8 +1040,6 @@ def main():
     assert not bad, f"guards failed on the timed outputs: {bad}"
 
     if rank == 0:
-        n = max(world, 1)
-        ups = n * B * args.steps / elapsed
         # ---- per-kernel timing with HIP events on the launch stream (second pass, same buffers) ----
         # (2 000 back-to-back launches each for the step's three kernels, a tenth as many untimed first.  Launched back to back
         # with itself the similarity kernel takes 14.4-14.5 us; between a search and a path kernel -- the one-batch-at-a-time
@@ -1024,11 +1126,7 @@ def main():
                                         "frac_of_8000": round(v["bytes"] / (v["us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 3),
                                         "frac_of_6300_achievable": round(v["bytes"] / (v["us"] * 1e-6) / 1e9 / 6300.0, 3)}
                                     for k, v in {**kernels, **(side if side_on else {})}.items()}}
-        out = {
-            "metric": "aligned utterances/sec + frames/sec, [B=64,T_text=200,T_mel=1000]",
-            "value": round(ups, 1), "unit": "utterances/s", "frames_per_s": round(ups * TY, 1),
-            "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        out.update({
             "ms_per_step_repeats": ([round(elapsed / args.steps * 1e3, 5)] +
                                     [round(x / args.steps * 1e3, 5) for x in extra]) if extra else None,
             "ms_per_step_median": round(float(np.median([elapsed] + extra)) / args.steps * 1e3, 5) if extra else None,
@@ -1039,28 +1137,9 @@ def main():
             "serial_ms_per_step": round(serial_elapsed / args.steps * 1e3, 5) if serial_elapsed else None,
             "serial_ms_per_step_expand_kernel": (round(serial_expand_elapsed / args.steps * 1e3, 5)
                                                  if serial_expand_elapsed else None),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "configs[1]: similarity (L2, C=80) + monotonic alignment search, "
-                                   "[B=64,T_text=200,T_mel=1000] fp32 per GPU, dense fp32 path + int32 durations out",
-                       "batch_per_gpu": B, "t_text": TX, "t_mel": TY, "c_att": C_ATT,
-                       "launch": "hipGraph" if step.graph is not None else "eager",
-                       "batches_in_flight": nstreams,
-                       "intermediate": ("log-probs [B,Tx,Ty] contiguous (--contiguous-logp)" if CONTIGUOUS_LOGP else
-                                        f"log-probs [B,Tx,Ty] at a row pitch of {step.ld} elements (rows on whole 128-byte lines: "
-                                        "aligner_softattn_ld -> aligner_maxpath_ld); inputs and outputs contiguous"),
-                       "path_stores": ("non-temporal (ALIGNER_F_STREAM_PATH) with the batches in flight, ordinary in the "
-                                       "serial figure" if stream_path else "ordinary"),
-                       "dense_path": {"batches_in_flight": args.path_mode, "serial": args.serial_path_mode,
-                                      "note": "fused = aligner_maxpath: one launch, zero workgroups on the idle CUs beside the search, "
-                                              "the utterances' workgroups write the ones; inline = zeros on a second graph branch beside the similarity kernel, the search "
-                                              "kernel writes the ones (ALIGNER_F_PATH_PREZEROED); branch = zeros beside the "
-                                              "search, then a scatter kernel; expand = one kernel behind the search"},
-                       "parallelism": f"batch-sharded x{n}" + (f", RCCL all_gather of durations every "
-                                                               f"{ge} steps" if n > 1 else "")},
             "roofline": roofline,
             "guards": guards,
-        }
+        })
         if n == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dev)
             out["speedup_vs_cpu_1thread"] = round(ups / out["cpu_baseline"]["value"], 1)

@@ -6,7 +6,8 @@ oracle/_ref/core.so by `make -C oracle ref`, and monotonic_align/__init__.py
 executed from /root/reference -- on seeded inputs and stores inputs + outputs as
 small data fixtures.  Nothing of the reference's text is stored, only vectors.
 
-    python tests/golden/make_golden.py        # rewrites the fixtures
+    python tests/golden/make_golden.py                    # rewrites the fixtures
+    python tests/golden/make_golden.py ref_random_cases   # ref_random_cases.json alone
 
 The fixtures pin oracle/maxpath_oracle.{c,py} (tests/test_oracle.py) and are
 the expected outputs of the HIP path in the `-m gpu` parity tests.
@@ -235,12 +236,46 @@ def txgtty_cases(ref):
     return n
 
 
+def random_cases(seed: int = 5, n: int = 120):
+    """Seeded random batches (ragged lengths; every third one with heavy ties, every third with -inf and NaN scores):
+    the inputs of tests/test_oracle.py::test_against_compiled_reference_when_present."""
+    rng = np.random.default_rng(seed)
+    for it in range(n):
+        B, Tx = int(rng.integers(1, 4)), int(rng.integers(1, 40))
+        Ty = int(rng.integers(Tx, 90))
+        v = rng.standard_normal((B, Tx, Ty)).astype(np.float32)
+        if it % 3 == 1:
+            v = np.round(v)                                        # heavy ties
+        if it % 3 == 2:
+            v[rng.random(v.shape) < 0.05] = -np.inf
+            v[rng.random(v.shape) < 0.03] = np.nan
+        ty = rng.integers(1, Ty + 1, B).astype(np.int32)
+        tx = np.array([rng.integers(1, min(Tx, t) + 1) for t in ty], np.int32)
+        yield v, tx, ty
+
+
+def ref_random_cases(ref):
+    """The reference's path and in-place mutated scores on random_cases(), as hashes of their bytes (bit for bit)."""
+    recs = []
+    for v, tx, ty in random_cases():
+        p, q = ref_core(v, tx, ty, ref)
+        recs.append({"value_sha256": synth.sha256_of(v), "path_sha256": synth.sha256_of(p), "q_sha256": synth.sha256_of(q)})
+    with open(os.path.join(HERE, "ref_random_cases.json"), "w") as f:
+        json.dump({"seed": 5, "cases": recs}, f, indent=0)
+        f.write("\n")
+    return len(recs)
+
+
 def main():
     O.build(ref=True)
     ref = O.load_ref()
     refw = O.load_ref_wrapper()
     if ref is None or refw is None:
         raise SystemExit("reference not available: run in the authoring container")
+    if sys.argv[1:] == ["ref_random_cases"]:                 # this fixture alone
+        print(f"wrote {ref_random_cases(ref)} random cases")
+        return
+    print(f"wrote {ref_random_cases(ref)} random cases")
     n = small_kats(ref)
     rec = appendix_a(ref, refw)
     wrapper_cases(refw)

@@ -1,5 +1,5 @@
 """The oracle against the golden vectors made by the real reference
-(tests/golden/make_golden.py) and against oracle/_ref when it is present."""
+(tests/golden/make_golden.py), and against oracle/_ref where it is built."""
 import numpy as np
 import pytest
 
@@ -144,25 +144,29 @@ def test_oracle_rejects_what_the_reference_rejects():
         O.maximum_path_c(p[0], v[0], t, u)
 
 
-def test_against_compiled_reference_when_present():
+def test_against_compiled_reference_when_present(golden_dir):
+    """120 seeded random batches (ties, -inf, NaN): path and mutated scores bit for bit against the compiled reference's,
+    stored as hashes (tests/golden/ref_random_cases.json, made by tests/golden/make_golden.py) -- and against oracle/_ref
+    itself, where it is built."""
+    import importlib.util
+    import json
+    import os
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(golden_dir, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    with open(os.path.join(golden_dir, "ref_random_cases.json")) as f:
+        rec = json.load(f)["cases"]
     ref = O.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref/core.so not built (reference tree absent)")
-    rng = np.random.default_rng(5)
-    for it in range(120):
-        B, Tx = int(rng.integers(1, 4)), int(rng.integers(1, 40))
-        Ty = int(rng.integers(Tx, 90))
-        v = rng.standard_normal((B, Tx, Ty)).astype(np.float32)
-        if it % 3 == 1:
-            v = np.round(v)                                        # heavy ties
-        if it % 3 == 2:
-            v[rng.random(v.shape) < 0.05] = -np.inf
-            v[rng.random(v.shape) < 0.03] = np.nan
-        ty = rng.integers(1, Ty + 1, B).astype(np.int32)
-        tx = np.array([rng.integers(1, min(Tx, t) + 1) for t in ty], np.int32)
+    cases = list(mg.random_cases())
+    assert len(cases) == len(rec) == 120
+    for (v, tx, ty), r in zip(cases, rec):
+        assert synth.sha256_of(v) == r["value_sha256"]            # the same inputs as the reference saw
         p1, q1 = _run(v, tx, ty)
-        q2 = v.copy()
-        p2 = np.zeros(v.shape, np.int32)
-        ref.maximum_path_c(p2, q2, tx, ty)
-        assert np.array_equal(p1, p2)
-        assert np.array_equal(q1.view(np.uint32), q2.view(np.uint32))
+        assert synth.sha256_of(p1) == r["path_sha256"]
+        assert synth.sha256_of(q1) == r["q_sha256"]
+        if ref is not None:
+            q2 = v.copy()
+            p2 = np.zeros(v.shape, np.int32)
+            ref.maximum_path_c(p2, q2, tx, ty)
+            assert np.array_equal(p1, p2)
+            assert np.array_equal(q1.view(np.uint32), q2.view(np.uint32))

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for r in 1 2; do for v in "$@"; do
 if [ "$v" = "-" ]; then unset ALIGNER_DEBUG_OPTIONS; else export ALIGNER_DEBUG_OPTIONS=$v; fi
 O=gpurun_out/c3ab; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/st -- python3 bench.py --config c3 --no-cpu-baseline > $O/b.json 2> $O/err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/st -- python3 bench.py --full --config c3 --no-cpu-baseline > $O/b.json 2> $O/err
 python3 - "$v" $O/b.json $(find $O/st -name '*kernel_stats.csv' | head -1) <<'PY'
 import csv, json, sys
 tag, bj, st = sys.argv[1:4]

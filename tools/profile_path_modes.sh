@@ -3,8 +3,8 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/pathmodes}; mkdir -p $O
 for m in expand branch inline; do
-  python3 bench.py --streams 1 --path-mode $m --no-repeats --no-cpu-baseline --steps 100 --warmup 10 > $O/bench_$m.json 2> $O/bench_$m.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$m -- python3 bench.py --streams 1 --path-mode $m --no-repeats --no-cpu-baseline --steps 100 --warmup 10 > /dev/null 2> $O/prof_$m.err
+  python3 bench.py --full --streams 1 --path-mode $m --no-repeats --no-cpu-baseline --steps 100 --warmup 10 > $O/bench_$m.json 2> $O/bench_$m.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$m -- python3 bench.py --full --streams 1 --path-mode $m --no-repeats --no-cpu-baseline --steps 100 --warmup 10 > /dev/null 2> $O/prof_$m.err
   f=$(find $O/stats_$m -name "*kernel_stats.csv" | head -1); cp $f $O/kernel_stats_$m.csv
   python3 - <<PY
 import json,csv
