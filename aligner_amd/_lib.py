@@ -76,7 +76,6 @@ SIGNATURES = {
     "aligner_softattn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
     "aligner_softattn_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
     "aligner_softattn_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
-    "aligner_conv1d_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "aligner_conv1d_prepared_bytes": (_sz, [_i, _i, _i]),
     "aligner_conv1d_prepare_f32": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp]),
     "aligner_conv1d_prepared_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1,8 +1,11 @@
-// Wide 1-D convolutions of the alignment encoders as a matrix-core GEMM that never waits for its operands
-// (gfx950).  y[b,o,t] = act(bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2]) -- the build-defined encoder stack of
+// The encoder's convolutions (gfx950) and their C entry points: the alignment encoders' 1-D convolutions
+// y[b,o,t] = act(bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2]) -- the build-defined encoder stack of
 // SURVEY.md 7.4 (no reference source: /root/reference/README.md:21-25,50 only names the branch).
 //
-// Round 3's kernel (softattn.hip, conv1d_prepared_kernel) moved every 16-channel chunk global -> VGPR -> split -> LDS
+// The layers run as a matrix-core GEMM that never waits for its operands (below).  A layer with no GEMM form
+// (conv_form() == CG_NONE) runs conv1d_prepared_kernel, on weights split once by conv_prep_kernel.
+//
+// Round 3's kernel (conv1d_prepared_kernel) moved every 16-channel chunk global -> VGPR -> split -> LDS
 // -> barrier: 36 MFMAs (~0.5 us) per ~1 us load round trip, 42 % of its wave-cycles in s_waitcnt, 0.075 of the
 // bf16 peak on the 512 -> 1024 k=3 layer.  This one is built around the load path instead:
 //
@@ -47,6 +50,7 @@ namespace aligner {
 typedef __attribute__((ext_vector_type(8))) __bf16 cg_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float cg_f32x4;
 typedef unsigned __attribute__((ext_vector_type(4))) cg_u32x4;
+typedef __attribute__((ext_vector_type(16))) float cg_f32x16;
 
 constexpr int CG_CH = 32;            // input channels per chunk (one k-step of v_mfma_f32_16x16x32_bf16)
 constexpr int CG_TO = 128;           // output channels per workgroup (4 waves x 2 tiles of 16)
@@ -873,6 +877,306 @@ static int launch_conv_fused(const ConvFusedParams &p, int nw, int B, size_t lds
     return ALIGNER_OK;
 }
 
+// ---- prepared weights: the split, fragment-ordered form of w, built once per weight tensor ----
+// Layout (both halves): [chunk = ceil(Cin/16)][tap][Cout padded to 128][channel half] of uint4 (8 bf16):
+// for one (chunk, tap) the fragments of consecutive output channels are contiguous, so a workgroup's
+// weight tile is K contiguous runs that it copies with coalesced 16-byte loads -- no gather, no VALU.
+// (Gathering w[o][i][tap] per workgroup cost ~300 scattered 4-byte wave-loads per chunk and CU: the
+// address coalescer, not the matrix pipe, set the pace: 466 us for the 512->1024 k=3 layer.)
+struct ConvPrep { size_t lo_off, total; int nch, cpad; };
+static ConvPrep conv_prep_layout(int Cout, int Cin, int K) {
+    ConvPrep L;
+    L.nch = (Cin + 15) / 16;
+    L.cpad = (Cout + 127) / 128 * 128;
+    const size_t half = (size_t)L.nch * K * L.cpad * 2 * sizeof(uint4);
+    L.lo_off = half;
+    L.total = 2 * half;
+    return L;
+}
+
+__global__ __launch_bounds__(256) void conv_prep_kernel(const float *__restrict__ w, uint4 *__restrict__ phi,
+                                                        uint4 *__restrict__ plo, int Cout, int Cin, int K, int cpad,
+                                                        int nfrag) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;          // fragment index: ((chunk*K + tap)*cpad + o)*2 + h
+    if (idx >= nfrag) return;
+    const int h = idx & 1, o = (idx >> 1) % cpad, ct = (idx >> 1) / cpad;
+    const int tap = ct % K, ch = ct / K;
+    cg_bf16x8 hv, lv;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+        const int i = 16 * ch + 8 * h + jj;
+        const float v = (o < Cout && i < Cin) ? w[((size_t)o * Cin + i) * K + tap] : 0.f;
+        __bf16 hh, ll;
+        cg_split(v, hh, ll);
+        hv[jj] = hh;
+        lv[jj] = ll;
+    }
+    phi[idx] = __builtin_bit_cast(uint4, hv);
+    plo[idx] = __builtin_bit_cast(uint4, lv);
+}
+
+// The convolution proper on prepared weights (aligner_conv1d_prepared_f32): the form of every layer with no GEMM
+// form (conv_form() == CG_NONE).
+// bf16 matrix cores with split operands: x = hi + lo (two bf16 halves of the fp32 value), product = hi*hi + hi*lo +
+// lo*hi in fp32 accumulators -- the similarity kernel's trick, ~2^-16 relative per product (far inside the 1e-4 the
+// encoders are held to) at 16/3 times the fp32 MFMA rate.  Reduction index k = (tap, in channel): one
+// v_mfma_f32_32x32x16_bf16 k-step is one tap of 16 input channels, so a chunk of 16 input channels is K k-steps.  The
+// weights come split and in fragment order (conv_prep_kernel); the activations are split once per workgroup and chunk
+// on their way into LDS, in fragment order: a fragment (8 consecutive channels of one frame / one output channel) is
+// one 16-byte LDS write and one conflict-free ds_read_b128.  Chunks are double-buffered in LDS and the next chunk's
+// global loads are in flight during the MFMAs (one barrier per chunk).
+// WO x WT waves, each AO x AT MFMA tiles of 32x32: workgroup tile (32*WO*AO) out channels x (32*WT*AT) frames.
+// <2,2,2,2> = 128x128 for wide layers; <3,2,1,1> = 96x64 (six waves) for the narrow (<= 96 channel) ones.
+// XV: T % 4 == 0, so the input rows can be read as aligned 16-byte quads (a task = 8 channels x 4 frames -> four
+// fragments); otherwise one frame per task.
+template <int K, int WO, int WT, int AO, int AT, bool XV, int SUB>
+__global__ __launch_bounds__(WO * WT * 64) void conv1d_prepared_kernel(const float *__restrict__ x,
+                                                                         const uint4 *__restrict__ phi,
+                                                                         const uint4 *__restrict__ plo,
+                                                                         const float *__restrict__ bias,
+                                                                         float *__restrict__ y, int Cin, int Cout, int T,
+                                                                         int cpad, int relu) {
+    constexpr int TO = 32 * WO * AO, TT = 32 * WT * AT, NTHR = WO * WT * 64;
+    constexpr int HALO = K / 2;
+    constexpr int F0 = XV ? 4 : HALO;             // LDS frame 0 <-> input frame t0 - F0
+    constexpr int XF = XV ? TT + 8 : TT + 2 * HALO;
+    // a chunk = SUB sub-chunks of 16 input channels (SUB = 4 for k = 1: one tap is too little work per barrier)
+    constexpr int XN1 = XF * 2, WN1 = K * TO * 2;
+    constexpr int XN = XN1 * SUB;                 // x fragments per chunk: [sub][frame][channel half]
+    constexpr int WN = WN1 * SUB;                 // w fragments per chunk: [sub][tap][out channel][channel half]
+    constexpr int BUF = 2 * XN + 2 * WN;          // uint4 per buffer: Xhi, Xlo, Whi, Wlo
+    extern __shared__ __attribute__((aligned(16))) unsigned char cv_smem[];
+    uint4 *lds = reinterpret_cast<uint4 *>(cv_smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = lane >> 5, l31 = lane & 31;
+    // (an XCD-aware tile map that keeps one output tile's weights in one XCD's L2 changed nothing on the
+    // 512->1024 layer and cost 50 % on the narrow ones: not kept)
+    const int b = blockIdx.z;
+    const int o0 = blockIdx.y * TO, t0 = blockIdx.x * TT;
+    const int wo = (wave / WT) * (32 * AO), wt = (wave % WT) * (32 * AT);
+    const float *xb = x + (size_t)b * Cin * T;
+    cg_f32x16 acc[AO][AT];
+#pragma unroll
+    for (int a = 0; a < AO; ++a)
+#pragma unroll
+        for (int c = 0; c < AT; ++c)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[a][c][e] = 0.f;
+
+    constexpr int WTASK = (WN + NTHR - 1) / NTHR;
+    constexpr int XQ1 = XV ? (XF / 4) * 2 : XN1;  // x tasks per sub-chunk
+    constexpr int XQ = XQ1 * SUB;
+    constexpr int XTASK = (XQ + NTHR - 1) / NTHR;
+    // one chunk's operands in registers, on their way to LDS: chunk c+1 is fetched while chunk c is multiplied
+    // (fetching two chunks ahead with two register sets was slower: 376 vs 325 us on the 512->1024 layer)
+    // One chunk's operands in registers on their way to LDS.  Native vector types: register arrays of HIP's
+    // uint4/float4 CLASSES stayed in scratch memory (320 instead of 201 us on the 512->1024 layer).
+    struct Stage {
+        cg_u32x4 wh[WTASK], wl[WTASK];
+        cg_f32x4 xq[XV ? XTASK : 1][8];
+        float xr[XV ? 1 : XTASK][8];
+    };
+    const int nch16 = (Cin + 15) / 16;
+    auto fetch = [&](Stage &R, int ch) {
+#pragma unroll
+        for (int j = 0; j < WTASK; ++j) {
+            int task = tid + NTHR * j;
+            task = task < WN ? task : WN - 1;
+            const int sub = task / WN1, t1 = task - sub * WN1;
+            const int tap = t1 / (TO * 2), r = t1 - tap * (TO * 2);
+            int c16 = ch * SUB + sub;                                     // past the last sub-chunk: any finite data
+            c16 = c16 < nch16 ? c16 : nch16 - 1;                          // (the x operand is zero there)
+            const size_t src = ((size_t)(c16 * K + tap) * cpad + o0) * 2 + r;
+            R.wh[j] = *reinterpret_cast<const cg_u32x4 *>(phi + src);
+            R.wl[j] = *reinterpret_cast<const cg_u32x4 *>(plo + src);
+        }
+        if (XV) {
+#pragma unroll
+            for (int j = 0; j < XTASK; ++j) {
+                const int task = tid + NTHR * j;
+                if (task < XQ) {
+                    const int sub = task / XQ1, t1 = task - sub * XQ1;
+                    const int i0 = 16 * (ch * SUB + sub);
+                    const int q = t1 >> 1, h = t1 & 1;
+                    const int t = t0 - 4 + 4 * q;                         // aligned quad: all in or all out
+                    const bool in = t >= 0 && t < T;
+                    const int tc = t < 0 ? 0 : (t > T - 4 ? T - 4 : t);   // unconditional loads, masked afterwards
+#pragma unroll
+                    for (int jj = 0; jj < 8; ++jj) {
+                        const int i = i0 + 8 * h + jj;
+                        const cg_f32x4 v = *reinterpret_cast<const cg_f32x4 *>(xb + (size_t)(i < Cin ? i : Cin - 1) * T + tc);
+                        const unsigned mk = (in && i < Cin) ? ~0u : 0u;
+                        cg_f32x4 mv;
+                        mv.x = and_maskf(v.x, mk); mv.y = and_maskf(v.y, mk); mv.z = and_maskf(v.z, mk); mv.w = and_maskf(v.w, mk);
+                        R.xq[j][jj] = mv;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < XTASK; ++j) {
+                int task = tid + NTHR * j;
+                task = task < XN ? task : XN - 1;
+                const int sub = task / XN1, t1 = task - sub * XN1;
+                const int i0 = 16 * (ch * SUB + sub);
+                const int f = t1 >> 1, h = t1 & 1;
+                const int t = t0 + f - F0;
+                const int tc = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int i = i0 + 8 * h + jj;
+                    const float v = xb[(size_t)(i < Cin ? i : Cin - 1) * T + tc];
+                    R.xr[j][jj] = and_maskf(v, (i < Cin && t >= 0 && t < T) ? ~0u : 0u);
+                }
+            }
+        }
+    };
+    auto pack_split = [&](const float (&r)[8], uint4 &hi, uint4 &lo) {
+        cg_bf16x8 h, l;
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) {
+            __bf16 hh, ll;
+            cg_split(r[jj], hh, ll);
+            h[jj] = hh;
+            l[jj] = ll;
+        }
+        hi = __builtin_bit_cast(uint4, h);
+        lo = __builtin_bit_cast(uint4, l);
+    };
+    auto multiply = [&](const uint4 *bufp) {
+        const uint4 *Xhi = bufp, *Xlo = bufp + XN, *Whi = bufp + 2 * XN, *Wlo = bufp + 2 * XN + WN;
+#pragma unroll
+        for (int st = 0; st < SUB * K; ++st) {
+            const int sub = st / K, tap = st - sub * K;
+            cg_bf16x8 ah[AO], al[AO], bh[AT], bl[AT];
+#pragma unroll
+            for (int a = 0; a < AO; ++a) {
+                const int idx = sub * WN1 + half * (K * TO) + tap * TO + wo + 32 * a + l31;       // [sub][channel half][tap][out channel]
+                ah[a] = __builtin_bit_cast(cg_bf16x8, Whi[idx]);
+                al[a] = __builtin_bit_cast(cg_bf16x8, Wlo[idx]);
+            }
+#pragma unroll
+            for (int c = 0; c < AT; ++c) {
+                const int idx = sub * XN1 + half * XF + (wt + 32 * c + l31 + tap - HALO + F0);     // [sub][channel half][frame]
+                bh[c] = __builtin_bit_cast(cg_bf16x8, Xhi[idx]);
+                bl[c] = __builtin_bit_cast(cg_bf16x8, Xlo[idx]);
+            }
+#pragma unroll
+            for (int a = 0; a < AO; ++a)
+#pragma unroll
+                for (int c = 0; c < AT; ++c) {
+                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[a], bh[c], acc[a][c], 0, 0, 0);
+                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bl[c], acc[a][c], 0, 0, 0);
+                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh[c], acc[a][c], 0, 0, 0);
+                }
+        }
+    };
+    auto stash = [&](const Stage &R, uint4 *bufp) {
+#pragma unroll
+        for (int j = 0; j < WTASK; ++j) {
+            const int task = tid + NTHR * j;
+            if (task < WN) {
+                // LDS keeps the two channel halves of a fragment row apart ([half][tap][out channel]): the 32 lanes of a
+                // half then read CONSECUTIVE 16-byte slots (interleaved, every ds_read_b128 was a 2-4-way bank conflict:
+                // 45 % of the LDS's busy cycles)
+                const int sub = task / WN1, t1 = task - sub * WN1;
+                const int dsti = sub * WN1 + (t1 & 1) * (K * TO) + (t1 >> 1);
+                *reinterpret_cast<cg_u32x4 *>(bufp + 2 * XN + dsti) = R.wh[j];
+                *reinterpret_cast<cg_u32x4 *>(bufp + 2 * XN + WN + dsti) = R.wl[j];
+            }
+        }
+        if (XV) {
+#pragma unroll
+            for (int j = 0; j < XTASK; ++j) {
+                const int task = tid + NTHR * j;
+                if (task < XQ) {
+                    const int sub = task / XQ1, t1 = task - sub * XQ1;
+                    const int q = t1 >> 1, h = t1 & 1;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        float r[8];
+#pragma unroll
+                        for (int jj = 0; jj < 8; ++jj)
+                            r[jj] = u == 0 ? R.xq[j][jj].x : u == 1 ? R.xq[j][jj].y : u == 2 ? R.xq[j][jj].z : R.xq[j][jj].w;
+                        const int fi = sub * XN1 + h * XF + (4 * q + u);
+                        pack_split(r, bufp[fi], bufp[XN + fi]);
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < XTASK; ++j) {
+                const int task = tid + NTHR * j;
+                if (task < XN) {
+                    const int sub = task / XN1, t1 = task - sub * XN1;
+                    const int fi = sub * XN1 + (t1 & 1) * XF + (t1 >> 1);
+                    pack_split(R.xr[j], bufp[fi], bufp[XN + fi]);
+                }
+            }
+        }
+    };
+    // software pipeline: chunk c+1 is fetched into registers while chunk c is multiplied out of LDS
+    // (fetching two chunks ahead with a second register set was slower: 304 vs 201 us on the 512->1024 layer)
+    const int nch = (Cin + 16 * SUB - 1) / (16 * SUB);
+    Stage R;
+    fetch(R, 0);
+    for (int ch = 0; ch < nch; ++ch) {
+        uint4 *bufp = lds + (ch & 1) * BUF;
+        stash(R, bufp);                           // (the other buffer may still be read by slower waves)
+        __syncthreads();
+        if (ch + 1 < nch) fetch(R, ch + 1);
+        multiply(bufp);
+    }
+    // C/D layout: col = lane&31 (frame), row = (e&3) + 8*(e>>2) + 4*half (out channel)
+#pragma unroll
+    for (int a = 0; a < AO; ++a)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int o = o0 + wo + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * half;
+            if (o >= Cout) continue;
+            const float bv = bias ? bias[o] : 0.f;
+#pragma unroll
+            for (int c = 0; c < AT; ++c) {
+                const int t = t0 + wt + 32 * c + l31;
+                if (t < T) {
+                    float v = acc[a][c][e] + bv;
+                    if (relu) v = fmaxf(v, 0.f);
+                    y[((size_t)b * Cout + o) * T + t] = v;
+                }
+            }
+        }
+}
+
+template <int K, int WO, int WT, int AO, int AT, int SUB>
+static int launch_conv_prepared_sub(dim3 grid, hipStream_t s, const float *x, const uint4 *phi, const uint4 *plo,
+                                    const float *bias, float *y, int Cin, int Cout, int T, int cpad, int relu) {
+    constexpr int TO = 32 * WO * AO, TT = 32 * WT * AT;
+    const bool xv = (T % 4) == 0;
+    const size_t xf = xv ? TT + 8 : TT + 2 * (K / 2);
+    const size_t lds = (size_t)2 * SUB * (2 * xf * 2 + 2 * K * TO * 2) * sizeof(uint4);
+    if (xv) {
+        auto kern = conv1d_prepared_kernel<K, WO, WT, AO, AT, true, SUB>;
+        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
+        hipLaunchKernelGGL(kern, grid, dim3(WO * WT * 64), lds, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
+    } else {
+        auto kern = conv1d_prepared_kernel<K, WO, WT, AO, AT, false, SUB>;
+        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
+        hipLaunchKernelGGL(kern, grid, dim3(WO * WT * 64), lds, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
+    }
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+
+template <int K, int WO, int WT, int AO, int AT>
+static int launch_conv_prepared(dim3 grid, hipStream_t s, const float *x, const uint4 *phi, const uint4 *plo,
+                                const float *bias, float *y, int Cin, int Cout, int T, int cpad, int relu) {
+    // k = 1 over many input channels: 64-channel chunks (one tap of 16 channels is too little work per barrier;
+    // 1024->80 on [64,.,200]: 67 -> 36 us).  Narrow inputs keep 16-channel chunks (padding to 64 would waste them).
+    if (K == 1 && Cin >= 256)
+        return launch_conv_prepared_sub<K, WO, WT, AO, AT, (K == 1 ? 4 : 1)>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
+    return launch_conv_prepared_sub<K, WO, WT, AO, AT, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
+}
+
 // ---- host side: which form a layer takes, its prepared weights, its launch ----
 enum { CG_NONE = 0, CG_WIDE = 1, CG_NARROW = 2 };
 struct ConvPlan { int form, FT, NT, nw, nx, cpad; size_t lds; };
@@ -955,17 +1259,17 @@ static int conv_launch(const ConvPlan &P, ConvGemmParams &p, int K, bool split, 
 #undef CG_NK
 }
 
-// ---- what softattn.hip's entry points call ----
-bool conv_gemm_applies(int Cin, int Cout, int K) { return conv_form(Cin, Cout, K) != CG_NONE; }
+// ---- what the C entry points below call ----
+static bool conv_gemm_applies(int Cin, int Cout, int K) { return conv_form(Cin, Cout, K) != CG_NONE; }
 
-size_t conv_gemm_prepared_bytes(int Cout, int Cin, int K) {
+static size_t conv_gemm_prepared_bytes(int Cout, int Cin, int K) {
     const int form = conv_form(Cin, Cout, K);
     if (form == CG_NONE) return 0;
     const int nch = (Cin + CG_CH - 1) / CG_CH;
     return (size_t)nch * K * (conv_cpad(form, Cout) / 16) * 2 * 64 * sizeof(uint4);
 }
 
-int conv_gemm_prepare(const float *w, void *prepared, int Cout, int Cin, int K, hipStream_t s) {
+static int conv_gemm_prepare(const float *w, void *prepared, int Cout, int Cin, int K, hipStream_t s) {
     const int form = conv_form(Cin, Cout, K);
     const int cpad = conv_cpad(form, Cout), nch = (Cin + CG_CH - 1) / CG_CH;
     const int nfrag = nch * K * (cpad / 16) * 64;
@@ -1031,7 +1335,7 @@ static FusedPlan fused_plan(const ConvStackLayer *L, int n, int B, int T) {
     return FusedPlan{};
 }
 
-size_t conv_stack_workspace_bytes(const ConvStackLayer *L, int n, int B, int T) {
+static size_t conv_stack_workspace_bytes(const ConvStackLayer *L, int n, int B, int T) {
     size_t img = 0, tmp = 0;
     for (int i = 0; i < n; ++i) {
         if (conv_plan(B, L[i].Cin, L[i].Cout, T, L[i].K).form == CG_NONE) return 0;
@@ -1045,8 +1349,8 @@ size_t conv_stack_workspace_bytes(const ConvStackLayer *L, int n, int B, int T) 
     return 2 * img + tmp;
 }
 
-int conv_stack_run(const float *x, const ConvStackLayer *L, int n, float *y, void *workspace, size_t workspace_bytes, int B, int T,
-                   hipStream_t s) {
+static int conv_stack_run(const float *x, const ConvStackLayer *L, int n, float *y, void *workspace, size_t workspace_bytes,
+                          int B, int T, hipStream_t s) {
     const size_t need = conv_stack_workspace_bytes(L, n, B, T);
     if (need == 0) return fail(ALIGNER_EDOM, "a layer of this stack has no GEMM form");
     if (workspace_bytes < need) return fail(ALIGNER_ENOSPC, "conv workspace %zu < %zu bytes", workspace_bytes, need);
@@ -1132,15 +1436,127 @@ int conv_stack_run(const float *x, const ConvStackLayer *L, int n, float *y, voi
     return ALIGNER_OK;
 }
 
-size_t conv_gemm_workspace_bytes(int B, int Cin, int Cout, int T, int K) {
+static size_t conv_gemm_workspace_bytes(int B, int Cin, int Cout, int T, int K) {
     ConvStackLayer l{nullptr, nullptr, Cin, Cout, K, 0};
     return conv_stack_workspace_bytes(&l, 1, B, T);
 }
 
-int conv_gemm_run(const float *x, const void *prepared, const float *bias, float *y, void *workspace, size_t workspace_bytes,
-                  int B, int Cin, int Cout, int T, int K, int relu, hipStream_t s) {
+static int conv_gemm_run(const float *x, const void *prepared, const float *bias, float *y, void *workspace,
+                         size_t workspace_bytes, int B, int Cin, int Cout, int T, int K, int relu, hipStream_t s) {
     ConvStackLayer l{prepared, bias, Cin, Cout, K, relu};
     return conv_stack_run(x, &l, 1, y, workspace, workspace_bytes, B, T, s);
 }
 
 }  // namespace aligner
+
+using namespace aligner;
+
+extern "C" {
+
+// prepared weights = [conv1d_prepared_kernel's image][for wide layers (conv_gemm_applies): conv_gemm_kernel's image]
+static size_t conv_prep_first_bytes(int Cout, int Cin, int K) { return align_up(conv_prep_layout(Cout, Cin, K).total, 256); }
+
+size_t aligner_conv1d_prepared_bytes(int Cout, int Cin, int K) {
+    if (Cout < 1 || Cin < 1 || (K != 1 && K != 3 && K != 5)) return 0;
+    return conv_prep_first_bytes(Cout, Cin, K) + (conv_gemm_applies(Cin, Cout, K) ? conv_gemm_prepared_bytes(Cout, Cin, K) : 0);
+}
+
+size_t aligner_conv1d_workspace_bytes(int B, int Cin, int Cout, int T, int K) {
+    if (B < 1 || Cout < 1 || Cin < 1 || T < 1 || !conv_gemm_applies(Cin, Cout, K)) return 0;
+    return conv_gemm_workspace_bytes(B, Cin, Cout, T, K);
+}
+
+int aligner_conv1d_prepare_f32(const float *w, void *prepared, size_t prepared_bytes, int Cout, int Cin, int K,
+                               void *stream) {
+    if (!w || !prepared) return fail(ALIGNER_EINVAL, "null pointer");
+    if (Cout < 1 || Cin < 1) return fail(ALIGNER_EINVAL, "bad shape");
+    if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
+    const ConvPrep L = conv_prep_layout(Cout, Cin, K);
+    const size_t need = aligner_conv1d_prepared_bytes(Cout, Cin, K);
+    if (prepared_bytes < need) return fail(ALIGNER_ENOSPC, "prepared buffer %zu < %zu bytes", prepared_bytes, need);
+    unsigned char *pp = static_cast<unsigned char *>(prepared);
+    const int nfrag = L.nch * K * L.cpad * 2;
+    hipLaunchKernelGGL(conv_prep_kernel, dim3((nfrag + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w,
+                       reinterpret_cast<uint4 *>(pp), reinterpret_cast<uint4 *>(pp + L.lo_off), Cout, Cin, K, L.cpad, nfrag);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    if (conv_gemm_applies(Cin, Cout, K))
+        return conv_gemm_prepare(w, pp + conv_prep_first_bytes(Cout, Cin, K), Cout, Cin, K, static_cast<hipStream_t>(stream));
+    return ALIGNER_OK;
+}
+
+int aligner_conv1d_prepared_ws_f32(const float *x, const void *prepared, const float *bias, float *y, void *workspace,
+                                   size_t workspace_bytes, int B, int Cin, int Cout, int T, int K, int relu, void *stream) {
+    if (!x || !prepared || !y) return fail(ALIGNER_EINVAL, "null pointer");
+    if (B < 0 || Cin < 1 || Cout < 1 || T < 1) return fail(ALIGNER_EINVAL, "bad shape");
+    if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
+    if (B == 0) return ALIGNER_OK;
+    const size_t nws = conv_gemm_applies(Cin, Cout, K) ? conv_gemm_workspace_bytes(B, Cin, Cout, T, K) : 0;
+    if (nws == 0)                                          // no GEMM form for this layer: conv1d_prepared_kernel, no workspace
+        return aligner_conv1d_prepared_f32(x, prepared, bias, y, B, Cin, Cout, T, K, relu, stream);
+    if (!workspace) return fail(ALIGNER_EINVAL, "this layer needs aligner_conv1d_workspace_bytes() of workspace");
+    const unsigned char *pp = static_cast<const unsigned char *>(prepared);
+    return conv_gemm_run(x, pp + conv_prep_first_bytes(Cout, Cin, K), bias, y, workspace, workspace_bytes, B, Cin, Cout, T, K,
+                         relu, static_cast<hipStream_t>(stream));
+}
+
+// A whole encoder stack in one call: the first layer's input is split once, every k = 1 layer reads the image its
+// producer's epilogue wrote (no fp32 round trip between layers), the last layer writes fp32 [B, Cout, T].
+static int conv_stack_convert(const aligner_conv_layer *layers, int n, ConvStackLayer *L) {
+    for (int i = 0; i < n; ++i) {
+        const aligner_conv_layer &a = layers[i];
+        if (a.Cin < 1 || a.Cout < 1 || (a.K != 1 && a.K != 3 && a.K != 5)) return fail(ALIGNER_EINVAL, "layer %d: bad shape", i);
+        if (i > 0 && a.Cin != layers[i - 1].Cout) return fail(ALIGNER_EINVAL, "layer %d: %d input channels after %d outputs", i, a.Cin, layers[i - 1].Cout);
+        const unsigned char *pp = static_cast<const unsigned char *>(a.prepared);
+        L[i] = ConvStackLayer{pp ? pp + conv_prep_first_bytes(a.Cout, a.Cin, a.K) : nullptr, a.bias, a.Cin, a.Cout, a.K, a.relu};
+    }
+    return ALIGNER_OK;
+}
+
+size_t aligner_conv_stack_workspace_bytes(const aligner_conv_layer *layers, int n_layers, int B, int T) {
+    if (!layers || n_layers < 1 || n_layers > 16 || B < 1 || T < 1) return 0;
+    ConvStackLayer L[16];
+    if (conv_stack_convert(layers, n_layers, L) != ALIGNER_OK) return 0;
+    for (int i = 0; i < n_layers; ++i)
+        if (!conv_gemm_applies(L[i].Cin, L[i].Cout, L[i].K)) return 0;
+    return conv_stack_workspace_bytes(L, n_layers, B, T);
+}
+
+int aligner_conv_stack_f32(const float *x, const aligner_conv_layer *layers, int n_layers, float *y, void *workspace,
+                           size_t workspace_bytes, int B, int T, void *stream) {
+    if (!x || !layers || !y || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
+    if (n_layers < 1 || n_layers > 16) return fail(ALIGNER_EINVAL, "1..16 layers");
+    if (B < 0 || T < 1) return fail(ALIGNER_EINVAL, "bad shape");
+    if (B == 0) return ALIGNER_OK;
+    ConvStackLayer L[16];
+    const int rc = conv_stack_convert(layers, n_layers, L);
+    if (rc != ALIGNER_OK) return rc;
+    for (int i = 0; i < n_layers; ++i)
+        if (!layers[i].prepared) return fail(ALIGNER_EINVAL, "layer %d: null prepared weights", i);
+    return conv_stack_run(x, L, n_layers, y, workspace, workspace_bytes, B, T, static_cast<hipStream_t>(stream));
+}
+
+int aligner_conv1d_prepared_f32(const float *x, const void *prepared, const float *bias, float *y, int B, int Cin,
+                                int Cout, int T, int K, int relu, void *stream) {
+    if (!x || !prepared || !y) return fail(ALIGNER_EINVAL, "null pointer");
+    if (B < 0 || Cin < 1 || Cout < 1 || T < 1) return fail(ALIGNER_EINVAL, "bad shape");
+    if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
+    if (B == 0) return ALIGNER_OK;
+    if (B > 65535) return fail(ALIGNER_EDOM, "grid too large");
+    const ConvPrep L = conv_prep_layout(Cout, Cin, K);
+    const unsigned char *pp = static_cast<const unsigned char *>(prepared);
+    const uint4 *phi = reinterpret_cast<const uint4 *>(pp), *plo = reinterpret_cast<const uint4 *>(pp + L.lo_off);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (Cout > 96) {
+        dim3 grid((T + 127) / 128, (Cout + 127) / 128, B);
+        if (grid.y > 65535) return fail(ALIGNER_EDOM, "grid too large");
+        if (K == 1) return launch_conv_prepared<1, 2, 2, 2, 2>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
+        if (K == 3) return launch_conv_prepared<3, 2, 2, 2, 2>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
+        return launch_conv_prepared<5, 2, 2, 2, 2>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
+    }
+    dim3 grid((T + 63) / 64, 1, B);
+    if (K == 1) return launch_conv_prepared<1, 3, 2, 1, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
+    if (K == 3) return launch_conv_prepared<3, 3, 2, 1, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
+    return launch_conv_prepared<5, 3, 2, 1, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 //
 // This is the build-defined spec of SURVEY.md 7.4 (the reference snapshot only
 // links the OTA paper, README.md:50); parity is against oracle/softattn_oracle.py.
+// Similarity only: the encoders' convolutions in front of it are convgemm.hip.
 //
 // Design (HBM-bound: 4*B*C*(Tx+Ty) bytes in, 4*B*Tx*Ty out, 2*B*Tx*Ty*C flops):
 //  * L2 distance expands to |q|^2 + |k|^2 - 2 k.q, so the only O(Tx*Ty*C) work is
@@ -29,25 +30,12 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "aligner_amd.h"
 #include "common.h"
 
 namespace aligner {
-
-// convgemm.hip: the wide layers' GEMM-structured convolution (operands pre-split, LDS-DMA staging)
-bool conv_gemm_applies(int Cin, int Cout, int K);
-size_t conv_gemm_prepared_bytes(int Cout, int Cin, int K);
-size_t conv_gemm_workspace_bytes(int B, int Cin, int Cout, int T, int K);
-int conv_gemm_prepare(const float *w, void *prepared, int Cout, int Cin, int K, hipStream_t s);
-int conv_gemm_run(const float *x, const void *prepared, const float *bias, float *y, void *workspace, size_t workspace_bytes,
-                  int B, int Cin, int Cout, int T, int K, int relu, hipStream_t s);
-struct ConvStackLayer { const void *prepared; const float *bias; int Cin, Cout, K, relu; };
-size_t conv_stack_workspace_bytes(const ConvStackLayer *L, int n, int B, int T);
-int conv_stack_run(const float *x, const ConvStackLayer *L, int n, float *y, void *workspace, size_t workspace_bytes, int B, int T,
-                   hipStream_t s);
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -1401,573 +1389,6 @@ __global__ __launch_bounds__(256) void softattn_exact_kernel(SoftAttnParams p, i
     }
 }
 
-// --------------------------------------------------------------------------
-// 1-D convolution of the text / mel encoders ("same" zero padding, K odd) on the matrix cores:
-// y[b,o,t] = act(bias[o] + sum_{i,k} w[o,i,k] x[b,i,t+k-K/2]) as a GEMM with
-// M = out channels, N = frames, reduction over (in channel, tap).  fp32-input MFMA
-// (v_mfma_f32_32x32x2_f32: exact fp32 fma chain, same 64 FLOP/clk/SIMD as the vector ALU but one
-// VGPR per operand and no VALU issue per FMA).  Workgroup tile 128 x 128 (4 waves, each 2x2 MFMA
-// tiles of 32x32), input channels staged through LDS 16 at a time: x rows with their halo once,
-// w as [ (i,k) ][ o ] so that both fragment reads are one conflict-free ds_read_b32 per lane.
-// --------------------------------------------------------------------------
-constexpr int CM_CI = 16;
-
-// WO x WT waves, each AO x AT MFMA tiles of 32x32: workgroup tile (32*WO*AO) out channels x (32*WT*AT) frames.
-// <2,2,2,2> = 128x128 for wide layers; <3,2,1,1> = 96x64 (six waves) for the narrow (<= 96 channel) ones.
-template <int K, int WO, int WT, int AO, int AT>
-__global__ __launch_bounds__(WO * WT * 64) void conv1d_mfma_kernel(const float *__restrict__ x,
-                                                                     const float *__restrict__ w,
-                                                                     const float *__restrict__ bias,
-                                                                     float *__restrict__ y, int Cin, int Cout, int T,
-                                                                     int relu) {
-    constexpr int CM_TO = 32 * WO * AO, CM_TT = 32 * WT * AT, NTHR = WO * WT * 64;
-    constexpr int HALO = K / 2;
-    constexpr int XLD = CM_TT + 2 * HALO + 1;                 // odd-ish row stride
-    constexpr int WLD = CM_TO + 4;                            // [ik][o], padded
-    __shared__ float xs[CM_CI * XLD];
-    __shared__ float wsm[CM_CI * K * WLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
-    const int b = blockIdx.z;
-    const int o0 = blockIdx.y * CM_TO, t0 = blockIdx.x * CM_TT;
-    const int wo = (wave / WT) * (32 * AO), wt = (wave % WT) * (32 * AT);   // this wave's corner inside the tile
-    const float *xb = x + (size_t)b * Cin * T;
-    f32x16 acc[AO][AT];
-#pragma unroll
-    for (int a = 0; a < AO; ++a)
-#pragma unroll
-        for (int c = 0; c < AT; ++c)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][c][e] = 0.f;
-
-    // register-staged pipeline: the next chunk's global loads are in flight while the MFMA loop
-    // runs on the current LDS image (issue early / write late)
-    constexpr int XN = (CM_CI * (CM_TT + 2 * HALO) + NTHR - 1) / NTHR;
-    constexpr int WN = (CM_CI * K * CM_TO + NTHR - 1) / NTHR;
-    float xr[XN], wr[WN];
-    auto fetch = [&](int i0) {
-#pragma unroll
-        for (int j = 0; j < XN; ++j) {
-            const int idx = tid + NTHR * j;
-            const int ii = idx / (CM_TT + 2 * HALO), tl = idx - ii * (CM_TT + 2 * HALO);
-            const int t = t0 + tl - HALO, i = i0 + ii;
-            xr[j] = (idx < CM_CI * (CM_TT + 2 * HALO) && i < Cin && t >= 0 && t < T) ? xb[(size_t)i * T + t] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int idx = tid + NTHR * j;
-            const int ol = idx / (CM_CI * K), ik = idx - ol * (CM_CI * K);      // ik = ii*K + k: contiguous in w
-            const int o = o0 + ol, i = i0 + ik / K;
-            wr[j] = (idx < CM_CI * K * CM_TO && o < Cout && i < Cin) ? w[((size_t)o * Cin + i0) * K + ik] : 0.f;
-        }
-    };
-    fetch(0);
-    for (int i0 = 0; i0 < Cin; i0 += CM_CI) {
-        __syncthreads();                                       // previous chunk's fragment reads are done
-#pragma unroll
-        for (int j = 0; j < XN; ++j) {
-            const int idx = tid + NTHR * j;
-            const int ii = idx / (CM_TT + 2 * HALO), tl = idx - ii * (CM_TT + 2 * HALO);
-            if (idx < CM_CI * (CM_TT + 2 * HALO)) xs[ii * XLD + tl] = xr[j];
-        }
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int idx = tid + NTHR * j;
-            const int ol = idx / (CM_CI * K), ik = idx - ol * (CM_CI * K);
-            if (idx < CM_CI * K * CM_TO) wsm[ik * WLD + ol] = wr[j];
-        }
-        __syncthreads();
-        if (i0 + CM_CI < Cin) fetch(i0 + CM_CI);
-#pragma unroll
-        for (int kk = 0; kk < CM_CI * K; kk += 2) {
-            // this lane's reduction index: kk + half  ->  (in channel, tap)
-            const int ik = kk + half;
-            const int ii = ik / K, tap = ik - ii * K;
-            float af[AO], bf[AT];
-#pragma unroll
-            for (int a = 0; a < AO; ++a) af[a] = wsm[ik * WLD + wo + 32 * a + l31];         // A[o][ik]
-#pragma unroll
-            for (int c = 0; c < AT; ++c) bf[c] = xs[ii * XLD + wt + 32 * c + l31 + tap];     // B[ik][t]
-#pragma unroll
-            for (int a = 0; a < AO; ++a)
-#pragma unroll
-                for (int c = 0; c < AT; ++c)
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a], bf[c], acc[a][c], 0, 0, 0);
-        }
-    }
-    // C/D layout: col = lane&31 (frame), row = (e&3) + 8*(e>>2) + 4*half (out channel)
-#pragma unroll
-    for (int a = 0; a < AO; ++a)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int o = o0 + wo + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * half;
-            if (o >= Cout) continue;
-            const float bv = bias ? bias[o] : 0.f;
-#pragma unroll
-            for (int c = 0; c < AT; ++c) {
-                const int t = t0 + wt + 32 * c + l31;
-                if (t < T) {
-                    float v = acc[a][c][e] + bv;
-                    if (relu) v = fmaxf(v, 0.f);
-                    y[((size_t)b * Cout + o) * T + t] = v;
-                }
-            }
-        }
-}
-
-// --------------------------------------------------------------------------
-// The same convolution on the bf16 matrix cores with split operands: x = hi + lo (two bf16 halves of the
-// fp32 value), product = hi*hi + hi*lo + lo*hi in fp32 accumulators -- the similarity kernel's trick,
-// ~2^-16 relative per product (far inside the 1e-4 the encoders are held to) at 16/3 times the fp32 MFMA
-// rate.  Reduction index k = (tap, in channel): one v_mfma_f32_32x32x16_bf16 k-step is one tap of 16 input
-// channels, so a chunk of 16 input channels is K k-steps.  Both operands are split once per workgroup and
-// chunk on their way into LDS, in fragment order: a fragment (8 consecutive channels of one frame / one
-// output channel) is one 16-byte LDS write and one conflict-free ds_read_b128.  Chunks are double-buffered
-// in LDS and the next chunk's global loads are in flight during the MFMAs (one barrier per chunk).
-// --------------------------------------------------------------------------
-template <int K, int WO, int WT, int AO, int AT>
-__global__ __launch_bounds__(WO * WT * 64) void conv1d_bf16x3_kernel(const float *__restrict__ x,
-                                                                       const float *__restrict__ w,
-                                                                       const float *__restrict__ bias,
-                                                                       float *__restrict__ y, int Cin, int Cout, int T,
-                                                                       int relu) {
-    constexpr int TO = 32 * WO * AO, TT = 32 * WT * AT, NTHR = WO * WT * 64;
-    constexpr int HALO = K / 2, XF = TT + 2 * HALO;
-    constexpr int XN = XF * 2;                    // x fragments per chunk: [frame][channel half]
-    constexpr int WN = K * TO * 2;                // w fragments per chunk: [tap][out channel][channel half]
-    constexpr int BUF = 2 * XN + 2 * WN;          // uint4 per buffer: Xhi, Xlo, Whi, Wlo
-    extern __shared__ __attribute__((aligned(16))) unsigned char cv_smem[];
-    uint4 *lds = reinterpret_cast<uint4 *>(cv_smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
-    const int b = blockIdx.z;
-    const int o0 = blockIdx.y * TO, t0 = blockIdx.x * TT;
-    const int wo = (wave / WT) * (32 * AO), wt = (wave % WT) * (32 * AT);
-    const float *xb = x + (size_t)b * Cin * T;
-    f32x16 acc[AO][AT];
-#pragma unroll
-    for (int a = 0; a < AO; ++a)
-#pragma unroll
-        for (int c = 0; c < AT; ++c)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][c][e] = 0.f;
-
-    constexpr int XTASK = (XN + NTHR - 1) / NTHR, WTASK = (WN + NTHR - 1) / NTHR;
-    float xr[XTASK][8], wr[WTASK][8];
-    // every load is unconditional (indices clamped, value masked afterwards): see and_mask()
-    auto fetch = [&](int i0) {
-#pragma unroll
-        for (int j = 0; j < XTASK; ++j) {
-            int task = tid + NTHR * j;
-            task = task < XN ? task : XN - 1;
-            const int f = task >> 1, h = task & 1;
-            const int t = t0 + f - HALO;
-            const int tc = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-                const int i = i0 + 8 * h + jj;
-                const float v = xb[(size_t)(i < Cin ? i : Cin - 1) * T + tc];
-                xr[j][jj] = and_mask(v, (i < Cin && t >= 0 && t < T) ? ~0u : 0u);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < WTASK; ++j) {
-            int task = tid + NTHR * j;            // tap fastest: the lanes of one output channel share two cache lines
-            task = task < WN ? task : WN - 1;
-            const int tap = task % K, rest = task / K;
-            const int h = rest & 1, o = o0 + (rest >> 1);
-            const size_t orow = (size_t)(o < Cout ? o : Cout - 1) * Cin;
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-                const int i = i0 + 8 * h + jj;
-                const float v = w[(orow + (i < Cin ? i : Cin - 1)) * K + tap];
-                wr[j][jj] = and_mask(v, (o < Cout && i < Cin) ? ~0u : 0u);
-            }
-        }
-    };
-    auto pack_split = [&](const float (&r)[8], uint4 &hi, uint4 &lo) {
-        bf16x8 h, l;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            __bf16 hh, ll;
-            split_bf16(r[jj], hh, ll);
-            h[jj] = hh;
-            l[jj] = ll;
-        }
-        hi = __builtin_bit_cast(uint4, h);
-        lo = __builtin_bit_cast(uint4, l);
-    };
-    auto stash = [&](uint4 *bufp) {
-#pragma unroll
-        for (int j = 0; j < XTASK; ++j) {
-            const int task = tid + NTHR * j;
-            if (task < XN) pack_split(xr[j], bufp[task], bufp[XN + task]);
-        }
-#pragma unroll
-        for (int j = 0; j < WTASK; ++j) {
-            const int task = tid + NTHR * j;
-            if (task < WN) {
-                const int tap = task % K, rest = task / K;
-                const int idx = (tap * TO + (rest >> 1)) * 2 + (rest & 1);
-                pack_split(wr[j], bufp[2 * XN + idx], bufp[2 * XN + WN + idx]);
-            }
-        }
-    };
-    fetch(0);
-    int it = 0;
-    for (int i0 = 0; i0 < Cin; i0 += 16, ++it) {
-        uint4 *bufp = lds + (it & 1) * BUF;
-        stash(bufp);                              // (the other buffer may still be read by slower waves)
-        __syncthreads();
-        if (i0 + 16 < Cin) fetch(i0 + 16);
-        const uint4 *Xhi = bufp, *Xlo = bufp + XN, *Whi = bufp + 2 * XN, *Wlo = bufp + 2 * XN + WN;
-#pragma unroll
-        for (int tap = 0; tap < K; ++tap) {
-            bf16x8 ah[AO], al[AO], bh[AT], bl[AT];
-#pragma unroll
-            for (int a = 0; a < AO; ++a) {
-                const int idx = (tap * TO + wo + 32 * a + l31) * 2 + half;
-                ah[a] = __builtin_bit_cast(bf16x8, Whi[idx]);
-                al[a] = __builtin_bit_cast(bf16x8, Wlo[idx]);
-            }
-#pragma unroll
-            for (int c = 0; c < AT; ++c) {
-                const int idx = (wt + 32 * c + l31 + tap) * 2 + half;
-                bh[c] = __builtin_bit_cast(bf16x8, Xhi[idx]);
-                bl[c] = __builtin_bit_cast(bf16x8, Xlo[idx]);
-            }
-#pragma unroll
-            for (int a = 0; a < AO; ++a)
-#pragma unroll
-                for (int c = 0; c < AT; ++c) {
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[a], bh[c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bl[c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh[c], acc[a][c], 0, 0, 0);
-                }
-        }
-    }
-    // C/D layout: col = lane&31 (frame), row = (e&3) + 8*(e>>2) + 4*half (out channel)
-#pragma unroll
-    for (int a = 0; a < AO; ++a)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int o = o0 + wo + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * half;
-            if (o >= Cout) continue;
-            const float bv = bias ? bias[o] : 0.f;
-#pragma unroll
-            for (int c = 0; c < AT; ++c) {
-                const int t = t0 + wt + 32 * c + l31;
-                if (t < T) {
-                    float v = acc[a][c][e] + bv;
-                    if (relu) v = fmaxf(v, 0.f);
-                    y[((size_t)b * Cout + o) * T + t] = v;
-                }
-            }
-        }
-}
-
-// ---- prepared weights: the split, fragment-ordered form of w, built once per weight tensor ----
-// Layout (both halves): [chunk = ceil(Cin/16)][tap][Cout padded to 128][channel half] of uint4 (8 bf16):
-// for one (chunk, tap) the fragments of consecutive output channels are contiguous, so a workgroup's
-// weight tile is K contiguous runs that it copies with coalesced 16-byte loads -- no gather, no VALU.
-// (Gathering w[o][i][tap] per workgroup cost ~300 scattered 4-byte wave-loads per chunk and CU: the
-// address coalescer, not the matrix pipe, set the pace: 466 us for the 512->1024 k=3 layer.)
-struct ConvPrep { size_t lo_off, total; int nch, cpad; };
-static ConvPrep conv_prep_layout(int Cout, int Cin, int K) {
-    ConvPrep L;
-    L.nch = (Cin + 15) / 16;
-    L.cpad = (Cout + 127) / 128 * 128;
-    const size_t half = (size_t)L.nch * K * L.cpad * 2 * sizeof(uint4);
-    L.lo_off = half;
-    L.total = 2 * half;
-    return L;
-}
-
-__global__ __launch_bounds__(256) void conv_prep_kernel(const float *__restrict__ w, uint4 *__restrict__ phi,
-                                                        uint4 *__restrict__ plo, int Cout, int Cin, int K, int cpad,
-                                                        int nfrag) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;          // fragment index: ((chunk*K + tap)*cpad + o)*2 + h
-    if (idx >= nfrag) return;
-    const int h = idx & 1, o = (idx >> 1) % cpad, ct = (idx >> 1) / cpad;
-    const int tap = ct % K, ch = ct / K;
-    bf16x8 hv, lv;
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) {
-        const int i = 16 * ch + 8 * h + jj;
-        const float v = (o < Cout && i < Cin) ? w[((size_t)o * Cin + i) * K + tap] : 0.f;
-        __bf16 hh, ll;
-        split_bf16(v, hh, ll);
-        hv[jj] = hh;
-        lv[jj] = ll;
-    }
-    phi[idx] = __builtin_bit_cast(uint4, hv);
-    plo[idx] = __builtin_bit_cast(uint4, lv);
-}
-
-// The convolution proper on prepared weights.  XV: T % 4 == 0, so the input rows can be read as aligned
-// 16-byte quads (a task = 8 channels x 4 frames -> four fragments); otherwise one frame per task.
-template <int K, int WO, int WT, int AO, int AT, bool XV, int SUB>
-__global__ __launch_bounds__(WO * WT * 64) void conv1d_prepared_kernel(const float *__restrict__ x,
-                                                                         const uint4 *__restrict__ phi,
-                                                                         const uint4 *__restrict__ plo,
-                                                                         const float *__restrict__ bias,
-                                                                         float *__restrict__ y, int Cin, int Cout, int T,
-                                                                         int cpad, int relu) {
-    constexpr int TO = 32 * WO * AO, TT = 32 * WT * AT, NTHR = WO * WT * 64;
-    constexpr int HALO = K / 2;
-    constexpr int F0 = XV ? 4 : HALO;             // LDS frame 0 <-> input frame t0 - F0
-    constexpr int XF = XV ? TT + 8 : TT + 2 * HALO;
-    // a chunk = SUB sub-chunks of 16 input channels (SUB = 4 for k = 1: one tap is too little work per barrier)
-    constexpr int XN1 = XF * 2, WN1 = K * TO * 2;
-    constexpr int XN = XN1 * SUB;                 // x fragments per chunk: [sub][frame][channel half]
-    constexpr int WN = WN1 * SUB;                 // w fragments per chunk: [sub][tap][out channel][channel half]
-    constexpr int BUF = 2 * XN + 2 * WN;          // uint4 per buffer: Xhi, Xlo, Whi, Wlo
-    extern __shared__ __attribute__((aligned(16))) unsigned char cv_smem[];
-    uint4 *lds = reinterpret_cast<uint4 *>(cv_smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
-    // (an XCD-aware tile map that keeps one output tile's weights in one XCD's L2 changed nothing on the
-    // 512->1024 layer and cost 50 % on the narrow ones: not kept)
-    const int b = blockIdx.z;
-    const int o0 = blockIdx.y * TO, t0 = blockIdx.x * TT;
-    const int wo = (wave / WT) * (32 * AO), wt = (wave % WT) * (32 * AT);
-    const float *xb = x + (size_t)b * Cin * T;
-    f32x16 acc[AO][AT];
-#pragma unroll
-    for (int a = 0; a < AO; ++a)
-#pragma unroll
-        for (int c = 0; c < AT; ++c)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][c][e] = 0.f;
-
-    constexpr int WTASK = (WN + NTHR - 1) / NTHR;
-    constexpr int XQ1 = XV ? (XF / 4) * 2 : XN1;  // x tasks per sub-chunk
-    constexpr int XQ = XQ1 * SUB;
-    constexpr int XTASK = (XQ + NTHR - 1) / NTHR;
-    // one chunk's operands in registers, on their way to LDS: chunk c+1 is fetched while chunk c is multiplied
-    // (fetching two chunks ahead with two register sets was slower: 376 vs 325 us on the 512->1024 layer)
-    // One chunk's operands in registers on their way to LDS.  Native vector types: register arrays of HIP's
-    // uint4/float4 CLASSES stayed in scratch memory (320 instead of 201 us on the 512->1024 layer).
-    typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
-    typedef float __attribute__((ext_vector_type(4))) f32x4v;
-    struct Stage {
-        u32x4 wh[WTASK], wl[WTASK];
-        f32x4v xq[XV ? XTASK : 1][8];
-        float xr[XV ? 1 : XTASK][8];
-    };
-    const int nch16 = (Cin + 15) / 16;
-    auto fetch = [&](Stage &R, int ch) {
-#pragma unroll
-        for (int j = 0; j < WTASK; ++j) {
-            int task = tid + NTHR * j;
-            task = task < WN ? task : WN - 1;
-            const int sub = task / WN1, t1 = task - sub * WN1;
-            const int tap = t1 / (TO * 2), r = t1 - tap * (TO * 2);
-            int c16 = ch * SUB + sub;                                     // past the last sub-chunk: any finite data
-            c16 = c16 < nch16 ? c16 : nch16 - 1;                          // (the x operand is zero there)
-            const size_t src = ((size_t)(c16 * K + tap) * cpad + o0) * 2 + r;
-            R.wh[j] = *reinterpret_cast<const u32x4 *>(phi + src);
-            R.wl[j] = *reinterpret_cast<const u32x4 *>(plo + src);
-        }
-        if (XV) {
-#pragma unroll
-            for (int j = 0; j < XTASK; ++j) {
-                const int task = tid + NTHR * j;
-                if (task < XQ) {
-                    const int sub = task / XQ1, t1 = task - sub * XQ1;
-                    const int i0 = 16 * (ch * SUB + sub);
-                    const int q = t1 >> 1, h = t1 & 1;
-                    const int t = t0 - 4 + 4 * q;                         // aligned quad: all in or all out
-                    const bool in = t >= 0 && t < T;
-                    const int tc = t < 0 ? 0 : (t > T - 4 ? T - 4 : t);   // unconditional loads, masked afterwards
-#pragma unroll
-                    for (int jj = 0; jj < 8; ++jj) {
-                        const int i = i0 + 8 * h + jj;
-                        const f32x4v v = *reinterpret_cast<const f32x4v *>(xb + (size_t)(i < Cin ? i : Cin - 1) * T + tc);
-                        const unsigned mk = (in && i < Cin) ? ~0u : 0u;
-                        f32x4v mv;
-                        mv.x = and_mask(v.x, mk); mv.y = and_mask(v.y, mk); mv.z = and_mask(v.z, mk); mv.w = and_mask(v.w, mk);
-                        R.xq[j][jj] = mv;
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < XTASK; ++j) {
-                int task = tid + NTHR * j;
-                task = task < XN ? task : XN - 1;
-                const int sub = task / XN1, t1 = task - sub * XN1;
-                const int i0 = 16 * (ch * SUB + sub);
-                const int f = t1 >> 1, h = t1 & 1;
-                const int t = t0 + f - F0;
-                const int tc = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int i = i0 + 8 * h + jj;
-                    const float v = xb[(size_t)(i < Cin ? i : Cin - 1) * T + tc];
-                    R.xr[j][jj] = and_mask(v, (i < Cin && t >= 0 && t < T) ? ~0u : 0u);
-                }
-            }
-        }
-    };
-    auto pack_split = [&](const float (&r)[8], uint4 &hi, uint4 &lo) {
-        bf16x8 h, l;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            __bf16 hh, ll;
-            split_bf16(r[jj], hh, ll);
-            h[jj] = hh;
-            l[jj] = ll;
-        }
-        hi = __builtin_bit_cast(uint4, h);
-        lo = __builtin_bit_cast(uint4, l);
-    };
-    auto multiply = [&](const uint4 *bufp) {
-        const uint4 *Xhi = bufp, *Xlo = bufp + XN, *Whi = bufp + 2 * XN, *Wlo = bufp + 2 * XN + WN;
-#pragma unroll
-        for (int st = 0; st < SUB * K; ++st) {
-            const int sub = st / K, tap = st - sub * K;
-            bf16x8 ah[AO], al[AO], bh[AT], bl[AT];
-#pragma unroll
-            for (int a = 0; a < AO; ++a) {
-                const int idx = sub * WN1 + half * (K * TO) + tap * TO + wo + 32 * a + l31;       // [sub][channel half][tap][out channel]
-                ah[a] = __builtin_bit_cast(bf16x8, Whi[idx]);
-                al[a] = __builtin_bit_cast(bf16x8, Wlo[idx]);
-            }
-#pragma unroll
-            for (int c = 0; c < AT; ++c) {
-                const int idx = sub * XN1 + half * XF + (wt + 32 * c + l31 + tap - HALO + F0);     // [sub][channel half][frame]
-                bh[c] = __builtin_bit_cast(bf16x8, Xhi[idx]);
-                bl[c] = __builtin_bit_cast(bf16x8, Xlo[idx]);
-            }
-#pragma unroll
-            for (int a = 0; a < AO; ++a)
-#pragma unroll
-                for (int c = 0; c < AT; ++c) {
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[a], bh[c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bl[c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh[c], acc[a][c], 0, 0, 0);
-                }
-        }
-    };
-    auto stash = [&](const Stage &R, uint4 *bufp) {
-#pragma unroll
-        for (int j = 0; j < WTASK; ++j) {
-            const int task = tid + NTHR * j;
-            if (task < WN) {
-                // LDS keeps the two channel halves of a fragment row apart ([half][tap][out channel]): the 32 lanes of a
-                // half then read CONSECUTIVE 16-byte slots (interleaved, every ds_read_b128 was a 2-4-way bank conflict:
-                // 45 % of the LDS's busy cycles)
-                const int sub = task / WN1, t1 = task - sub * WN1;
-                const int dsti = sub * WN1 + (t1 & 1) * (K * TO) + (t1 >> 1);
-                *reinterpret_cast<u32x4 *>(bufp + 2 * XN + dsti) = R.wh[j];
-                *reinterpret_cast<u32x4 *>(bufp + 2 * XN + WN + dsti) = R.wl[j];
-            }
-        }
-        if (XV) {
-#pragma unroll
-            for (int j = 0; j < XTASK; ++j) {
-                const int task = tid + NTHR * j;
-                if (task < XQ) {
-                    const int sub = task / XQ1, t1 = task - sub * XQ1;
-                    const int q = t1 >> 1, h = t1 & 1;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        float r[8];
-#pragma unroll
-                        for (int jj = 0; jj < 8; ++jj)
-                            r[jj] = u == 0 ? R.xq[j][jj].x : u == 1 ? R.xq[j][jj].y : u == 2 ? R.xq[j][jj].z : R.xq[j][jj].w;
-                        const int fi = sub * XN1 + h * XF + (4 * q + u);
-                        pack_split(r, bufp[fi], bufp[XN + fi]);
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < XTASK; ++j) {
-                const int task = tid + NTHR * j;
-                if (task < XN) {
-                    const int sub = task / XN1, t1 = task - sub * XN1;
-                    const int fi = sub * XN1 + (t1 & 1) * XF + (t1 >> 1);
-                    pack_split(R.xr[j], bufp[fi], bufp[XN + fi]);
-                }
-            }
-        }
-    };
-    // software pipeline: chunk c+1 is fetched into registers while chunk c is multiplied out of LDS
-    // (fetching two chunks ahead with a second register set was slower: 304 vs 201 us on the 512->1024 layer)
-    const int nch = (Cin + 16 * SUB - 1) / (16 * SUB);
-    Stage R;
-    fetch(R, 0);
-    for (int ch = 0; ch < nch; ++ch) {
-        uint4 *bufp = lds + (ch & 1) * BUF;
-        stash(R, bufp);                           // (the other buffer may still be read by slower waves)
-        __syncthreads();
-        if (ch + 1 < nch) fetch(R, ch + 1);
-        multiply(bufp);
-    }
-    // C/D layout: col = lane&31 (frame), row = (e&3) + 8*(e>>2) + 4*half (out channel)
-#pragma unroll
-    for (int a = 0; a < AO; ++a)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int o = o0 + wo + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * half;
-            if (o >= Cout) continue;
-            const float bv = bias ? bias[o] : 0.f;
-#pragma unroll
-            for (int c = 0; c < AT; ++c) {
-                const int t = t0 + wt + 32 * c + l31;
-                if (t < T) {
-                    float v = acc[a][c][e] + bv;
-                    if (relu) v = fmaxf(v, 0.f);
-                    y[((size_t)b * Cout + o) * T + t] = v;
-                }
-            }
-        }
-}
-
-template <int K, int WO, int WT, int AO, int AT, int SUB>
-static int launch_conv_prepared_sub(dim3 grid, hipStream_t s, const float *x, const uint4 *phi, const uint4 *plo,
-                                    const float *bias, float *y, int Cin, int Cout, int T, int cpad, int relu) {
-    constexpr int TO = 32 * WO * AO, TT = 32 * WT * AT;
-    const bool xv = (T % 4) == 0;
-    const size_t xf = xv ? TT + 8 : TT + 2 * (K / 2);
-    const size_t lds = (size_t)2 * SUB * (2 * xf * 2 + 2 * K * TO * 2) * sizeof(uint4);
-    if (xv) {
-        auto kern = conv1d_prepared_kernel<K, WO, WT, AO, AT, true, SUB>;
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
-        hipLaunchKernelGGL(kern, grid, dim3(WO * WT * 64), lds, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
-    } else {
-        auto kern = conv1d_prepared_kernel<K, WO, WT, AO, AT, false, SUB>;
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
-        hipLaunchKernelGGL(kern, grid, dim3(WO * WT * 64), lds, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
-    }
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    return ALIGNER_OK;
-}
-
-template <int K, int WO, int WT, int AO, int AT>
-static int launch_conv_prepared(dim3 grid, hipStream_t s, const float *x, const uint4 *phi, const uint4 *plo,
-                                const float *bias, float *y, int Cin, int Cout, int T, int cpad, int relu) {
-    // k = 1 over many input channels: 64-channel chunks (one tap of 16 channels is too little work per barrier;
-    // 1024->80 on [64,.,200]: 67 -> 36 us).  Narrow inputs keep 16-channel chunks (padding to 64 would waste them).
-    if (K == 1 && Cin >= 256)
-        return launch_conv_prepared_sub<K, WO, WT, AO, AT, (K == 1 ? 4 : 1)>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
-    return launch_conv_prepared_sub<K, WO, WT, AO, AT, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, cpad, relu);
-}
-
-template <int K, int WO, int WT, int AO, int AT>
-static int launch_conv_bf16x3(dim3 grid, hipStream_t s, const float *x, const float *w, const float *bias, float *y,
-                              int Cin, int Cout, int T, int relu) {
-    constexpr int TO = 32 * WO * AO, TT = 32 * WT * AT;
-    const size_t lds = (size_t)2 * (2 * (TT + 2 * (K / 2)) * 2 + 2 * K * TO * 2) * sizeof(uint4);
-    auto kern = conv1d_bf16x3_kernel<K, WO, WT, AO, AT>;
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
-    hipLaunchKernelGGL(kern, grid, dim3(WO * WT * 64), lds, s, x, w, bias, y, Cin, Cout, T, relu);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    return ALIGNER_OK;
-}
-
 struct SaLayout { size_t hi_off, lo_off, kn_off, total; int RT, KS; };
 
 static SaLayout sa_layout(int B, int C, int Tx) {
@@ -2122,153 +1543,6 @@ int aligner_softattn_ld(const float *keys, const float *queries, const int32_t *
     if (L.KS == 5) return multi ? launch_softattn<5, 7, true>(p, ws, L, s) : launch_softattn<5, 7, false>(p, ws, L, s);
     if (L.KS == 8) return multi ? launch_softattn<8, 7, true>(p, ws, L, s) : launch_softattn<8, 7, false>(p, ws, L, s);
     return multi ? launch_softattn<16, 4, true>(p, ws, L, s) : launch_softattn<16, 4, false>(p, ws, L, s);
-}
-
-// prepared weights = [conv1d_prepared_kernel's image][for wide layers (conv_gemm_applies): conv_gemm_kernel's image]
-static size_t conv_prep_first_bytes(int Cout, int Cin, int K) { return align_up(conv_prep_layout(Cout, Cin, K).total, 256); }
-
-size_t aligner_conv1d_prepared_bytes(int Cout, int Cin, int K) {
-    if (Cout < 1 || Cin < 1 || (K != 1 && K != 3 && K != 5)) return 0;
-    return conv_prep_first_bytes(Cout, Cin, K) + (conv_gemm_applies(Cin, Cout, K) ? conv_gemm_prepared_bytes(Cout, Cin, K) : 0);
-}
-
-size_t aligner_conv1d_workspace_bytes(int B, int Cin, int Cout, int T, int K) {
-    if (B < 1 || Cout < 1 || Cin < 1 || T < 1 || !conv_gemm_applies(Cin, Cout, K)) return 0;
-    return conv_gemm_workspace_bytes(B, Cin, Cout, T, K);
-}
-
-int aligner_conv1d_prepare_f32(const float *w, void *prepared, size_t prepared_bytes, int Cout, int Cin, int K,
-                               void *stream) {
-    if (!w || !prepared) return fail(ALIGNER_EINVAL, "null pointer");
-    if (Cout < 1 || Cin < 1) return fail(ALIGNER_EINVAL, "bad shape");
-    if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
-    const ConvPrep L = conv_prep_layout(Cout, Cin, K);
-    const size_t need = aligner_conv1d_prepared_bytes(Cout, Cin, K);
-    if (prepared_bytes < need) return fail(ALIGNER_ENOSPC, "prepared buffer %zu < %zu bytes", prepared_bytes, need);
-    unsigned char *pp = static_cast<unsigned char *>(prepared);
-    const int nfrag = L.nch * K * L.cpad * 2;
-    hipLaunchKernelGGL(conv_prep_kernel, dim3((nfrag + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w,
-                       reinterpret_cast<uint4 *>(pp), reinterpret_cast<uint4 *>(pp + L.lo_off), Cout, Cin, K, L.cpad, nfrag);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    if (conv_gemm_applies(Cin, Cout, K))
-        return conv_gemm_prepare(w, pp + conv_prep_first_bytes(Cout, Cin, K), Cout, Cin, K, static_cast<hipStream_t>(stream));
-    return ALIGNER_OK;
-}
-
-int aligner_conv1d_prepared_ws_f32(const float *x, const void *prepared, const float *bias, float *y, void *workspace,
-                                   size_t workspace_bytes, int B, int Cin, int Cout, int T, int K, int relu, void *stream) {
-    if (!x || !prepared || !y) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Cin < 1 || Cout < 1 || T < 1) return fail(ALIGNER_EINVAL, "bad shape");
-    if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
-    if (B == 0) return ALIGNER_OK;
-    static const bool no_gemm = [] { const char *e = getenv("ALIGNER_CONV_NO_GEMM"); return e && e[0] == '1'; }();
-    const size_t nws = (conv_gemm_applies(Cin, Cout, K) && !no_gemm) ? conv_gemm_workspace_bytes(B, Cin, Cout, T, K) : 0;
-    if (nws == 0)                                          // no GEMM form for this layer: conv1d_prepared_kernel, no workspace
-        return aligner_conv1d_prepared_f32(x, prepared, bias, y, B, Cin, Cout, T, K, relu, stream);
-    if (!workspace) return fail(ALIGNER_EINVAL, "this layer needs aligner_conv1d_workspace_bytes() of workspace");
-    const unsigned char *pp = static_cast<const unsigned char *>(prepared);
-    return conv_gemm_run(x, pp + conv_prep_first_bytes(Cout, Cin, K), bias, y, workspace, workspace_bytes, B, Cin, Cout, T, K,
-                         relu, static_cast<hipStream_t>(stream));
-}
-
-// A whole encoder stack in one call: the first layer's input is split once, every k = 1 layer reads the image its
-// producer's epilogue wrote (no fp32 round trip between layers), the last layer writes fp32 [B, Cout, T].
-static int conv_stack_convert(const aligner_conv_layer *layers, int n, ConvStackLayer *L) {
-    for (int i = 0; i < n; ++i) {
-        const aligner_conv_layer &a = layers[i];
-        if (a.Cin < 1 || a.Cout < 1 || (a.K != 1 && a.K != 3 && a.K != 5)) return fail(ALIGNER_EINVAL, "layer %d: bad shape", i);
-        if (i > 0 && a.Cin != layers[i - 1].Cout) return fail(ALIGNER_EINVAL, "layer %d: %d input channels after %d outputs", i, a.Cin, layers[i - 1].Cout);
-        const unsigned char *pp = static_cast<const unsigned char *>(a.prepared);
-        L[i] = ConvStackLayer{pp ? pp + conv_prep_first_bytes(a.Cout, a.Cin, a.K) : nullptr, a.bias, a.Cin, a.Cout, a.K, a.relu};
-    }
-    return ALIGNER_OK;
-}
-
-size_t aligner_conv_stack_workspace_bytes(const aligner_conv_layer *layers, int n_layers, int B, int T) {
-    if (!layers || n_layers < 1 || n_layers > 16 || B < 1 || T < 1) return 0;
-    ConvStackLayer L[16];
-    if (conv_stack_convert(layers, n_layers, L) != ALIGNER_OK) return 0;
-    for (int i = 0; i < n_layers; ++i)
-        if (!conv_gemm_applies(L[i].Cin, L[i].Cout, L[i].K)) return 0;
-    return conv_stack_workspace_bytes(L, n_layers, B, T);
-}
-
-int aligner_conv_stack_f32(const float *x, const aligner_conv_layer *layers, int n_layers, float *y, void *workspace,
-                           size_t workspace_bytes, int B, int T, void *stream) {
-    if (!x || !layers || !y || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
-    if (n_layers < 1 || n_layers > 16) return fail(ALIGNER_EINVAL, "1..16 layers");
-    if (B < 0 || T < 1) return fail(ALIGNER_EINVAL, "bad shape");
-    if (B == 0) return ALIGNER_OK;
-    ConvStackLayer L[16];
-    const int rc = conv_stack_convert(layers, n_layers, L);
-    if (rc != ALIGNER_OK) return rc;
-    for (int i = 0; i < n_layers; ++i)
-        if (!layers[i].prepared) return fail(ALIGNER_EINVAL, "layer %d: null prepared weights", i);
-    return conv_stack_run(x, L, n_layers, y, workspace, workspace_bytes, B, T, static_cast<hipStream_t>(stream));
-}
-
-int aligner_conv1d_prepared_f32(const float *x, const void *prepared, const float *bias, float *y, int B, int Cin,
-                                int Cout, int T, int K, int relu, void *stream) {
-    if (!x || !prepared || !y) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Cin < 1 || Cout < 1 || T < 1) return fail(ALIGNER_EINVAL, "bad shape");
-    if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
-    if (B == 0) return ALIGNER_OK;
-    if (B > 65535) return fail(ALIGNER_EDOM, "grid too large");
-    const ConvPrep L = conv_prep_layout(Cout, Cin, K);
-    const unsigned char *pp = static_cast<const unsigned char *>(prepared);
-    const uint4 *phi = reinterpret_cast<const uint4 *>(pp), *plo = reinterpret_cast<const uint4 *>(pp + L.lo_off);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (Cout > 96) {
-        dim3 grid((T + 127) / 128, (Cout + 127) / 128, B);
-        if (grid.y > 65535) return fail(ALIGNER_EDOM, "grid too large");
-        if (K == 1) return launch_conv_prepared<1, 2, 2, 2, 2>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
-        if (K == 3) return launch_conv_prepared<3, 2, 2, 2, 2>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
-        return launch_conv_prepared<5, 2, 2, 2, 2>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
-    }
-    dim3 grid((T + 63) / 64, 1, B);
-    if (K == 1) return launch_conv_prepared<1, 3, 2, 1, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
-    if (K == 3) return launch_conv_prepared<3, 3, 2, 1, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
-    return launch_conv_prepared<5, 3, 2, 1, 1>(grid, s, x, phi, plo, bias, y, Cin, Cout, T, L.cpad, relu);
-}
-
-int aligner_conv1d_f32(const float *x, const float *w, const float *bias, float *y, int B, int Cin, int Cout,
-                       int T, int K, int relu, void *stream) {
-    if (!x || !w || !y) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Cin < 1 || Cout < 1 || T < 1) return fail(ALIGNER_EINVAL, "bad shape");
-    if (B == 0) return ALIGNER_OK;
-    if (B > 65535) return fail(ALIGNER_EDOM, "grid too large");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
-    // ALIGNER_CONV_FP32=1 selects the exact-fp32 MFMA kernel (v_mfma_f32_32x32x2_f32); the default splits the
-    // operands into bf16 halves (three bf16 MFMAs per product, ~2^-16 relative)
-    static const bool exact_fp32 = [] { const char *e = getenv("ALIGNER_CONV_FP32"); return e && e[0] == '1'; }();
-    if (!exact_fp32) {
-        if (Cout > 96) {
-            dim3 grid((T + 127) / 128, (Cout + 127) / 128, B);
-            if (grid.y > 65535) return fail(ALIGNER_EDOM, "grid too large");
-            if (K == 1) return launch_conv_bf16x3<1, 2, 2, 2, 2>(grid, s, x, w, bias, y, Cin, Cout, T, relu);
-            if (K == 3) return launch_conv_bf16x3<3, 2, 2, 2, 2>(grid, s, x, w, bias, y, Cin, Cout, T, relu);
-            return launch_conv_bf16x3<5, 2, 2, 2, 2>(grid, s, x, w, bias, y, Cin, Cout, T, relu);
-        }
-        dim3 grid((T + 63) / 64, 1, B);
-        if (K == 1) return launch_conv_bf16x3<1, 3, 2, 1, 1>(grid, s, x, w, bias, y, Cin, Cout, T, relu);
-        if (K == 3) return launch_conv_bf16x3<3, 3, 2, 1, 1>(grid, s, x, w, bias, y, Cin, Cout, T, relu);
-        return launch_conv_bf16x3<5, 3, 2, 1, 1>(grid, s, x, w, bias, y, Cin, Cout, T, relu);
-    }
-    if (Cout > 96) {
-        dim3 grid((T + 127) / 128, (Cout + 127) / 128, B), block(256);
-        if (grid.y > 65535) return fail(ALIGNER_EDOM, "grid too large");
-        if (K == 1) hipLaunchKernelGGL((conv1d_mfma_kernel<1, 2, 2, 2, 2>), grid, block, 0, s, x, w, bias, y, Cin, Cout, T, relu);
-        if (K == 3) hipLaunchKernelGGL((conv1d_mfma_kernel<3, 2, 2, 2, 2>), grid, block, 0, s, x, w, bias, y, Cin, Cout, T, relu);
-        if (K == 5) hipLaunchKernelGGL((conv1d_mfma_kernel<5, 2, 2, 2, 2>), grid, block, 0, s, x, w, bias, y, Cin, Cout, T, relu);
-    } else {
-        dim3 grid((T + 63) / 64, 1, B), block(384);
-        if (K == 1) hipLaunchKernelGGL((conv1d_mfma_kernel<1, 3, 2, 1, 1>), grid, block, 0, s, x, w, bias, y, Cin, Cout, T, relu);
-        if (K == 3) hipLaunchKernelGGL((conv1d_mfma_kernel<3, 3, 2, 1, 1>), grid, block, 0, s, x, w, bias, y, Cin, Cout, T, relu);
-        if (K == 5) hipLaunchKernelGGL((conv1d_mfma_kernel<5, 3, 2, 1, 1>), grid, block, 0, s, x, w, bias, y, Cin, Cout, T, relu);
-    }
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    return ALIGNER_OK;
 }
 
 }  // extern "C"

@@ -96,25 +96,6 @@ def invalidate_prepared() -> None:
     _prepared.clear()
 
 
-def conv1d_raw(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False
-               ) -> torch.Tensor:
-    """conv1d() through aligner_conv1d_f32: raw weights, no preparation buffer (slower: every workgroup
-    splits its weight tile itself; ALIGNER_CONV_FP32=1 selects the exact-fp32 MFMA kernel)."""
-    _lib.require_gpu()
-    x = _chk(x, "x"); weight = _chk(weight, "weight")
-    bias = _chk(bias, "bias") if bias is not None else None
-    B, Cin, T = x.shape
-    Cout, Cin2, K = weight.shape
-    if Cin2 != Cin:
-        raise ValueError("channel mismatch")
-    y = torch.empty((B, Cout, T), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().aligner_conv1d_f32(x.data_ptr(), weight.data_ptr(),
-                                                  None if bias is None else bias.data_ptr(), y.data_ptr(),
-                                                  B, Cin, Cout, T, K, int(relu), _stream(x.device)))
-    return y
-
-
 def soft_attention(keys_enc: torch.Tensor, queries_enc: torch.Tensor, t_x: Optional[torch.Tensor] = None,
                    prior: Optional[torch.Tensor] = None, temperature: float = 0.0005, sim: str = "l2",
                    want_soft: bool = False, out: Optional[torch.Tensor] = None,

@@ -35,8 +35,9 @@ extern "C" {
  *    the prepared-weights image of round 4 (old image + the GEMM form's) and the forward-sum / search workspaces of round 4
  *    are what the *_bytes functions of THIS version return: size every buffer with them, never with constants;
  *    new entry points aligner_softattn_ld / aligner_maxpath_ld (a row pitch for the pipeline's own intermediate) and the
- *    test flag ALIGNER_F_TEST_IMPATIENT_FIRST_HALF. */
-#define ALIGNER_ABI_VERSION 4
+ *    test flag ALIGNER_F_TEST_IMPATIENT_FIRST_HALF.
+ * 5: the convolution on raw (unprepared) weights left the library: prepare the weights once. */
+#define ALIGNER_ABI_VERSION 5
 
 /* error codes */
 #define ALIGNER_OK       0
@@ -309,14 +310,10 @@ int aligner_softattn_ld(const float *keys_dev, const float *queries_dev,
                         int B, int C, int Tx, int Ty,
                         float temperature, int sim, void *stream);
 
-/* y[b,o,t] = act( bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2] ), zero padded
- * ("same"), K odd; the 1-D conv of the text / mel encoders. relu: 0 or 1. */
-int aligner_conv1d_f32(const float *x_dev, const float *w_dev, const float *bias_dev,
-                       float *y_dev, int B, int Cin, int Cout, int T, int K,
-                       int relu, void *stream);
-
 /*
- * The same convolution with the weights prepared once (split into bf16 halves, in the matrix cores'
+ * y[b,o,t] = act( bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2] ), zero padded
+ * ("same"), K odd; the 1-D conv of the text / mel encoders. relu: 0 or 1.
+ * Weights prepared once (split into bf16 halves, in the matrix cores'
  * fragment order): aligner_conv1d_prepare_f32 writes aligner_conv1d_prepared_bytes(Cout,Cin,K) bytes,
  * aligner_conv1d_prepared_f32 consumes them.  Products are hi*hi + hi*lo + lo*hi in fp32 accumulators
  * (~2^-16 relative per product).  This is the fast path of the encoders: prepare per weight update.

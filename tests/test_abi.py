@@ -29,8 +29,8 @@ def test_header_symbols_all_exported(built_lib):
     assert set(names) == set(_lib.SIGNATURES), "ctypes table and header disagree"
 
 
-def test_abi_version_and_errors(built_lib):
-    assert built_lib.aligner_abi_version() == 4
+def test_abi_version_5_and_errors(built_lib):
+    assert built_lib.aligner_abi_version() == 5
     assert built_lib.aligner_maxpath_workspace_bytes(64, 200, 1000) > 64 * 32 * 256 * 4
     assert built_lib.aligner_maxpath_workspace_bytes(1, 0, 5) == 0
     # argument validation happens before any HIP call

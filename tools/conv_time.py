@@ -17,6 +17,5 @@ for (B, Ci, Co, T, K) in [(64, 512, 1024, 200, 3), (64, 1024, 80, 200, 1), (64, 
     st = torch.cuda.current_stream().cuda_stream
     tp = ev(lambda: lib.aligner_conv1d_prepare_f32(w.data_ptr(), prep.data_ptr(), n, Co, Ci, K, st))
     tc = ev(lambda: lib.aligner_conv1d_prepared_f32(x.data_ptr(), prep.data_ptr(), bias.data_ptr(), y.data_ptr(), B, Ci, Co, T, K, 1, st))
-    tr = ev(lambda: lib.aligner_conv1d_f32(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), B, Ci, Co, T, K, 1, st))
     fl = 2.0 * B * T * Co * Ci * K
-    print(f"[{B},{Ci}->{Co},T={T},k={K}] prep {tp:.1f} us, prepared conv {tc:.1f} us ({fl/tc/1e6:.1f} TFLOP/s fp32-equivalent), raw-weight kernel {tr:.1f} us")
+    print(f"[{B},{Ci}->{Co},T={T},k={K}] prep {tp:.1f} us, prepared conv {tc:.1f} us ({fl/tc/1e6:.1f} TFLOP/s fp32-equivalent)")
