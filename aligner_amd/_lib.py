@@ -83,6 +83,11 @@ SIGNATURES = {
     "aligner_conv1d_prepared_ws_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
     "aligner_conv_stack_workspace_bytes": (_sz, [_c.POINTER(ConvLayer), _i, _i, _i]),
     "aligner_conv_stack_f32": (_i, [_vp, _c.POINTER(ConvLayer), _i, _vp, _vp, _sz, _i, _i, _vp]),
+    "aligner_softattn_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aligner_softattn_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
+    "aligner_conv1d_prepare_transposed_f32": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp]),
+    "aligner_conv1d_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "aligner_conv1d_backward_weight_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
     "aligner_forward_sum_workspace_bytes": (_sz, [_i, _i, _i]),
     "aligner_forward_sum_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "aligner_forward_sum_ctc_workspace_bytes": (_sz, [_i, _i, _i]),

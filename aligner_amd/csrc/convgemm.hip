@@ -85,8 +85,14 @@ __device__ __forceinline__ void cg_split(float v, __bf16 &hi, __bf16 &lo) {
 
 // weights -> fragment order.  B operand of the MFMA (k = input channel, n = output channel): lane l holds
 // w[o = 16*tile + (l & 15)][i = 32*chunk + 8*(l >> 4) + j][tap], j = 0..7.
+// tr: w is the weight of the layer this one is the transpose of ([Cin][Cout][K]; w'[o][i][tap] = w[i][o][K-1-tap]: the
+// input gradient of that layer, aligner_conv1d_prepare_transposed_f32)
+__device__ __forceinline__ size_t cg_widx(int o, int i, int tap, int Cout, int Cin, int K, int tr) {
+    return tr ? ((size_t)i * Cout + o) * K + (K - 1 - tap) : ((size_t)o * Cin + i) * K + tap;
+}
+
 __global__ __launch_bounds__(256) void conv_gemm_wprep_kernel(const float *__restrict__ w, uint4 *__restrict__ wp, int Cout,
-                                                              int Cin, int K, int cpad, int nfrag) {
+                                                              int Cin, int K, int cpad, int nfrag, int tr) {
     const int idx = blockIdx.x * 256 + threadIdx.x;          // ((chunk*K + tap)*(cpad/16) + tile)*64 + lane
     if (idx >= nfrag) return;
     const int lane = idx & 63, tile = (idx >> 6) % (cpad / 16), ct = (idx >> 6) / (cpad / 16);
@@ -96,7 +102,7 @@ __global__ __launch_bounds__(256) void conv_gemm_wprep_kernel(const float *__res
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int i = CG_CH * ch + 8 * (lane >> 4) + j;
-        const float v = (o < Cout && i < Cin) ? w[((size_t)o * Cin + i) * K + tap] : 0.f;
+        const float v = (o < Cout && i < Cin) ? w[cg_widx(o, i, tap, Cout, Cin, K, tr)] : 0.f;
         __bf16 hh, ll;
         cg_split(v, hh, ll);
         hv[j] = hh;
@@ -896,7 +902,7 @@ static ConvPrep conv_prep_layout(int Cout, int Cin, int K) {
 
 __global__ __launch_bounds__(256) void conv_prep_kernel(const float *__restrict__ w, uint4 *__restrict__ phi,
                                                         uint4 *__restrict__ plo, int Cout, int Cin, int K, int cpad,
-                                                        int nfrag) {
+                                                        int nfrag, int tr) {
     const int idx = blockIdx.x * 256 + threadIdx.x;          // fragment index: ((chunk*K + tap)*cpad + o)*2 + h
     if (idx >= nfrag) return;
     const int h = idx & 1, o = (idx >> 1) % cpad, ct = (idx >> 1) / cpad;
@@ -905,7 +911,7 @@ __global__ __launch_bounds__(256) void conv_prep_kernel(const float *__restrict_
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
         const int i = 16 * ch + 8 * h + jj;
-        const float v = (o < Cout && i < Cin) ? w[((size_t)o * Cin + i) * K + tap] : 0.f;
+        const float v = (o < Cout && i < Cin) ? w[cg_widx(o, i, tap, Cout, Cin, K, tr)] : 0.f;
         __bf16 hh, ll;
         cg_split(v, hh, ll);
         hv[jj] = hh;
@@ -1269,12 +1275,12 @@ static size_t conv_gemm_prepared_bytes(int Cout, int Cin, int K) {
     return (size_t)nch * K * (conv_cpad(form, Cout) / 16) * 2 * 64 * sizeof(uint4);
 }
 
-static int conv_gemm_prepare(const float *w, void *prepared, int Cout, int Cin, int K, hipStream_t s) {
+static int conv_gemm_prepare(const float *w, void *prepared, int Cout, int Cin, int K, int tr, hipStream_t s) {
     const int form = conv_form(Cin, Cout, K);
     const int cpad = conv_cpad(form, Cout), nch = (Cin + CG_CH - 1) / CG_CH;
     const int nfrag = nch * K * (cpad / 16) * 64;
     hipLaunchKernelGGL(conv_gemm_wprep_kernel, dim3((nfrag + 255) / 256), dim3(256), 0, s, w, static_cast<uint4 *>(prepared),
-                       Cout, Cin, K, cpad, nfrag);
+                       Cout, Cin, K, cpad, nfrag, tr);
     ALIGNER_HIP_CHECK(hipGetLastError());
     return ALIGNER_OK;
 }
@@ -1466,8 +1472,10 @@ size_t aligner_conv1d_workspace_bytes(int B, int Cin, int Cout, int T, int K) {
     return conv_gemm_workspace_bytes(B, Cin, Cout, T, K);
 }
 
-int aligner_conv1d_prepare_f32(const float *w, void *prepared, size_t prepared_bytes, int Cout, int Cin, int K,
-                               void *stream) {
+// both prepare entry points: the image of w [Cout][Cin][K] (tr = 0), or of its transpose (tr = 1: Cout, Cin are the
+// transpose's, w is [Cin][Cout][K])
+static int conv_prepare(const float *w, void *prepared, size_t prepared_bytes, int Cout, int Cin, int K, int tr,
+                        void *stream) {
     if (!w || !prepared) return fail(ALIGNER_EINVAL, "null pointer");
     if (Cout < 1 || Cin < 1) return fail(ALIGNER_EINVAL, "bad shape");
     if (K != 1 && K != 3 && K != 5) return fail(ALIGNER_EDOM, "kernel size %d not supported (1, 3, 5)", K);
@@ -1477,11 +1485,21 @@ int aligner_conv1d_prepare_f32(const float *w, void *prepared, size_t prepared_b
     unsigned char *pp = static_cast<unsigned char *>(prepared);
     const int nfrag = L.nch * K * L.cpad * 2;
     hipLaunchKernelGGL(conv_prep_kernel, dim3((nfrag + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w,
-                       reinterpret_cast<uint4 *>(pp), reinterpret_cast<uint4 *>(pp + L.lo_off), Cout, Cin, K, L.cpad, nfrag);
+                       reinterpret_cast<uint4 *>(pp), reinterpret_cast<uint4 *>(pp + L.lo_off), Cout, Cin, K, L.cpad, nfrag, tr);
     ALIGNER_HIP_CHECK(hipGetLastError());
     if (conv_gemm_applies(Cin, Cout, K))
-        return conv_gemm_prepare(w, pp + conv_prep_first_bytes(Cout, Cin, K), Cout, Cin, K, static_cast<hipStream_t>(stream));
+        return conv_gemm_prepare(w, pp + conv_prep_first_bytes(Cout, Cin, K), Cout, Cin, K, tr, static_cast<hipStream_t>(stream));
     return ALIGNER_OK;
+}
+
+int aligner_conv1d_prepare_f32(const float *w, void *prepared, size_t prepared_bytes, int Cout, int Cin, int K,
+                               void *stream) {
+    return conv_prepare(w, prepared, prepared_bytes, Cout, Cin, K, 0, stream);
+}
+
+int aligner_conv1d_prepare_transposed_f32(const float *w, void *prepared, size_t prepared_bytes, int Cout, int Cin, int K,
+                                          void *stream) {
+    return conv_prepare(w, prepared, prepared_bytes, Cin, Cout, K, 1, stream);
 }
 
 int aligner_conv1d_prepared_ws_f32(const float *x, const void *prepared, const float *bias, float *y, void *workspace,

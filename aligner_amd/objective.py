@@ -88,7 +88,8 @@ def forward_sum_loss(logp: torch.Tensor, t_x: torch.Tensor, t_y: torch.Tensor, b
                      reduction: str = "mean", zero_infinity: bool = False, length_normalize: bool = False) -> torch.Tensor:
     """The OTA aligner's ForwardSumLoss as an autograd function on the GPU kernels: forward_sum() with its gradient
     attached, so that `forward_sum_loss(logp, t_x, t_y).backward()` reaches whatever differentiable torch code produced
-    `logp` (this package's `soft_attention()` kernel is forward-only: SURVEY 8 scopes the front end's forward pass).  One launch pair computes loss AND gradient in the forward pass (both sweeps side by side); backward()
+    `logp` -- alignment_encoder() / soft_attention() included: their backward is HIP as well (soft_attention_backward(),
+    conv1d_backward()), so the gradient reaches the encoder weights.  One launch pair computes loss AND gradient in the forward pass (both sweeps side by side); backward()
     only scales.  blank_logprob = -1.0: the published CTC form (None: the plain monotonic form).  reduction: "mean" (a plain
     mean over the batch), "sum" or "none".  The two switches of torch.nn.CTCLoss that published aligner code is usually
     written with (neither the reference snapshot nor SNIPPETS.md holds that code: parity unpinned) are here as options, off

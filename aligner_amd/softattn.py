@@ -34,6 +34,8 @@ def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
 _workspaces = _lib.StreamWorkspaces(zero=False)
 _conv_workspaces = _lib.StreamWorkspaces(zero=False)      # split activations of the wide conv layers
 _prepared: dict = {}          # (weight ptr, shape, device, stream) -> (version, prepared weights, weight)
+_prepared_t: dict = {}        # the same for the transposed weights (the input gradient's convolution)
+_bwd_workspaces = _lib.StreamWorkspaces(zero=False)       # the backward passes' column statistics / weight-gradient partials
 
 
 def _workspace(device, nbytes: int) -> torch.Tensor:
@@ -67,8 +69,19 @@ def _prepared_weights(weight: torch.Tensor, device) -> torch.Tensor:
     return ent[1]
 
 
+def _needs_grad(*tensors) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
-    """y = act(conv1d(x, weight, bias, padding=K//2)); x [B,Cin,T], weight [Cout,Cin,K], K in {1,3,5}."""
+    """y = act(conv1d(x, weight, bias, padding=K//2)); x [B,Cin,T], weight [Cout,Cin,K], K in {1,3,5}.
+    Differentiable (conv1d_backward()) when grad is enabled and x, weight or bias requires grad."""
+    if _needs_grad(x, weight, bias):
+        return _Conv1d.apply(x, weight, bias, relu)
+    return _conv1d(x, weight, bias, relu)
+
+
+def _conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], relu: bool) -> torch.Tensor:
     _lib.require_gpu()
     x = _chk(x, "x"); weight = _chk(weight, "weight")
     bias = _chk(bias, "bias") if bias is not None else None
@@ -90,10 +103,104 @@ def conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     return y
 
 
+def _prepared_weights_transposed(weight: torch.Tensor, device) -> torch.Tensor:
+    """The prepared image of w'[i,o,k] = w[o,i,K-1-k] (aligner_conv1d_prepare_transposed_f32): the input gradient of the
+    layer is the forward convolution of its output gradient with it.  Cached like _prepared_weights(), in a table of its
+    own, re-prepared when the weight's version counter moves."""
+    lib = _lib.load()
+    Cout, Cin, K = weight.shape
+    key = (weight.data_ptr(), Cout, Cin, K, device, _stream(device))
+    ent = _prepared_t.get(key)
+    if ent is None or ent[0] != weight._version:
+        nprep = lib.aligner_conv1d_prepared_bytes(Cin, Cout, K)
+        if nprep == 0:
+            raise ValueError(f"kernel size {K} not supported (1, 3, 5)")
+        prep = ent[1] if ent is not None else torch.empty(nprep, dtype=torch.uint8, device=device)
+        _lib.check(lib.aligner_conv1d_prepare_transposed_f32(weight.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K,
+                                                             _stream(device)))
+        if ent is None and len(_prepared_t) >= 256:
+            _prepared_t.pop(next(iter(_prepared_t)))
+        _prepared_t[key] = (weight._version, prep, weight)
+        return prep
+    return ent[1]
+
+
+def conv1d_backward(x: torch.Tensor, weight: torch.Tensor, y: Optional[torch.Tensor], grad_y: torch.Tensor, relu: bool,
+                    need_x: bool = True, need_w: bool = True, need_b: bool = True
+                    ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Gradients of y = act(conv1d(x, weight, bias)) (act = ReLU when relu) given grad_y = dL/dy: (grad_x [B,Cin,T],
+    grad_w [Cout,Cin,K], grad_b [Cout]), fp32, None where not asked for.  y (the layer's output) is needed with relu only.
+    grad_w / grad_b: aligner_conv1d_backward_weight_f32; grad_x: the forward convolution of the masked grad_y with the
+    transposed weights (aligner_conv1d_prepare_transposed_f32 + aligner_conv1d_prepared_ws_f32)."""
+    _lib.require_gpu()
+    x = _chk(x, "x"); weight = _chk(weight, "weight"); gy = _chk(grad_y, "grad_y")
+    B, Cin, T = x.shape
+    Cout, Cin2, K = weight.shape
+    if Cin2 != Cin or tuple(gy.shape) != (B, Cout, T):
+        raise ValueError("shape mismatch")
+    if relu:
+        if y is None:
+            raise ValueError("relu needs the layer's output y")
+        y = _chk(y, "y")
+        if tuple(y.shape) != (B, Cout, T):
+            raise ValueError("y must be [B,Cout,T]")
+    dev = x.device
+    lib = _lib.load()
+    gx = gw = gb = None
+    with torch.cuda.device(dev):
+        gyp = gy
+        if relu and need_x:
+            gyp = torch.empty_like(gy)
+        if need_w:
+            gw = torch.empty((Cout, Cin, K), dtype=torch.float32, device=dev)
+        if need_b:
+            gb = torch.empty((Cout,), dtype=torch.float32, device=dev)
+        if need_w or need_b or (relu and need_x):
+            nws = lib.aligner_conv1d_backward_workspace_bytes(B, Cin, Cout, T, K)
+            ws = _bwd_workspaces.get(dev, nws) if (need_w or need_b) and nws else None
+            _lib.check(lib.aligner_conv1d_backward_weight_f32(
+                x.data_ptr(), y.data_ptr() if relu else None, gy.data_ptr(), gyp.data_ptr() if (relu and need_x) else None,
+                None if gw is None else gw.data_ptr(), None if gb is None else gb.data_ptr(),
+                None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
+                B, Cin, Cout, T, K, int(relu), _stream(dev)))
+        if need_x:
+            prep = _prepared_weights_transposed(weight, dev)
+            gx = torch.empty((B, Cin, T), dtype=torch.float32, device=dev)
+            nws = lib.aligner_conv1d_workspace_bytes(B, Cout, Cin, T, K)
+            ws = _conv_workspaces.get(dev, nws) if nws else None
+            _lib.check(lib.aligner_conv1d_prepared_ws_f32(gyp.data_ptr(), prep.data_ptr(), None, gx.data_ptr(),
+                                                          None if ws is None else ws.data_ptr(), nws,
+                                                          B, Cout, Cin, T, K, 0, _stream(dev)))
+    return gx, gw, gb
+
+
+class _Conv1d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        ctx.set_materialize_grads(False)
+        xf, wf = _chk(x, "x"), _chk(weight, "weight")
+        y = _conv1d(xf, wf, bias, relu)
+        ctx.relu = relu
+        ctx.dtypes = (x.dtype, weight.dtype, None if bias is None else bias.dtype)
+        ctx.save_for_backward(xf, wf, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None:
+            return None, None, None, None
+        x, w, y = ctx.saved_tensors
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        gx, gw, gb = conv1d_backward(x, w, y, gy, ctx.relu, need_x=nx, need_w=nw, need_b=nb)
+        dx, dw, db = ctx.dtypes
+        return (None if gx is None else gx.to(dx), None if gw is None else gw.to(dw), None if gb is None else gb.to(db), None)
+
+
 def invalidate_prepared() -> None:
     """Drop every prepared (split-bf16) weight image: call after weight updates that bypass torch's version
     counter (`p.data.copy_()`, EMA through `.data`, writes through a storage alias)."""
     _prepared.clear()
+    _prepared_t.clear()
 
 
 def soft_attention(keys_enc: torch.Tensor, queries_enc: torch.Tensor, t_x: Optional[torch.Tensor] = None,
@@ -109,7 +216,24 @@ def soft_attention(keys_enc: torch.Tensor, queries_enc: torch.Tensor, t_x: Optio
 
     keys_enc [B,C,T_text], queries_enc [B,C,T_mel] fp32 (channel-major, as the conv
     encoders emit).  Rows i >= t_x[b] are masked to -inf.  logp_dtype torch.bfloat16 writes the log-probs as
-    bf16 (half the traffic; align() / maximum_path() read them as they are)."""
+    bf16 (half the traffic; align() / maximum_path() read them as they are).
+
+    Differentiable in keys_enc / queries_enc (soft_attention_backward(), through logp and soft) when grad is enabled and
+    either requires grad; the prior gets no gradient (a prior that requires grad, and `out`, are refused then)."""
+    if _needs_grad(keys_enc, queries_enc) or (torch.is_grad_enabled() and prior is not None and prior.requires_grad):
+        if out is not None:
+            raise ValueError("out= is not supported with autograd (keys_enc / queries_enc require grad)")
+        if prior is not None and prior.requires_grad:
+            raise ValueError("the prior gets no gradient: pass prior.detach()")
+        if logp_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("logp_dtype must be torch.float32 or torch.bfloat16")
+        logp, soft = _SoftAttention.apply(keys_enc, queries_enc, t_x, prior, float(temperature), sim, want_soft, logp_dtype,
+                                          pitched)
+        return logp, soft
+    return _soft_attention(keys_enc, queries_enc, t_x, prior, temperature, sim, want_soft, out, logp_dtype, pitched)
+
+
+def _soft_attention(keys_enc, queries_enc, t_x, prior, temperature, sim, want_soft, out, logp_dtype, pitched):
     _lib.require_gpu()
     k = _chk(keys_enc, "keys_enc"); q = _chk(queries_enc, "queries_enc")
     B, C, Tx = k.shape
@@ -129,7 +253,8 @@ def soft_attention(keys_enc: torch.Tensor, queries_enc: torch.Tensor, t_x: Optio
         raise ValueError("logp_dtype must be torch.float32 or torch.bfloat16")
     if out is None and pitched and prior is None and not want_soft and Tx <= 224 and C in (80, 128) and Ty % 4 == 0:
         try:
-            return soft_attention(k, q, t_x=t_x, temperature=temperature, sim=sim, out=pitched_logp(B, Tx, Ty, dev, logp_dtype))
+            return _soft_attention(k, q, t_x, None, temperature, sim, False, pitched_logp(B, Tx, Ty, dev, logp_dtype), logp_dtype,
+                                   False)
         except _lib.AlignerError as e:          # (a sharp temperature: the exact-product kernel has no row pitch)
             if e.code != _lib.EDOM:
                 raise
@@ -152,6 +277,79 @@ def soft_attention(keys_enc: torch.Tensor, queries_enc: torch.Tensor, t_x: Optio
             None if soft is None else soft.data_ptr(), ws.data_ptr(), ws.numel(),
             B, C, Tx, Ty, float(temperature), simc, _stream(dev)))
     return logp, soft
+
+
+def soft_attention_backward(keys_enc: torch.Tensor, queries_enc: torch.Tensor, grad_logp: torch.Tensor,
+                            t_x: Optional[torch.Tensor] = None, prior: Optional[torch.Tensor] = None,
+                            temperature: float = 0.0005, sim: str = "l2", grad_soft: Optional[torch.Tensor] = None,
+                            need_keys: bool = True, need_queries: bool = True
+                            ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Gradients of soft_attention()'s logp (and soft) w.r.t. keys_enc [B,C,T_text] and queries_enc [B,C,T_mel], given
+    grad_logp = dL/dlogp and optionally grad_soft = dL/dsoft ([B,T_text,T_mel]) and the forward's own t_x / prior /
+    temperature / sim (aligner_softattn_backward_f32: the logits are recomputed, not read).  Returns (grad_keys,
+    grad_queries) in fp32, None where not asked for.  Masked rows get a zero gradient; the prior gets none."""
+    _lib.require_gpu()
+    if not (need_keys or need_queries):
+        return None, None
+    k = _chk(keys_enc, "keys_enc"); q = _chk(queries_enc, "queries_enc")
+    B, C, Tx = k.shape
+    B2, C2, Ty = q.shape
+    if B != B2 or C != C2:
+        raise ValueError("keys/queries shape mismatch")
+    gl = _chk(grad_logp, "grad_logp")
+    if tuple(gl.shape) != (B, Tx, Ty):
+        raise ValueError("grad_logp must be [B,T_text,T_mel]")
+    gs = None
+    if grad_soft is not None:
+        gs = _chk(grad_soft, "grad_soft")
+        if tuple(gs.shape) != (B, Tx, Ty):
+            raise ValueError("grad_soft must be [B,T_text,T_mel]")
+    dev = k.device
+    if t_x is not None:
+        t_x = t_x.to(device=dev, dtype=torch.int32).contiguous()
+    if prior is not None:
+        prior = _chk(prior, "prior")
+        if tuple(prior.shape) != (B, Tx, Ty):
+            raise ValueError("prior must be [B,T_text,T_mel]")
+    simc = {"l2": _lib.SIM_L2, "dot": _lib.SIM_DOT}[sim]
+    gk = torch.empty((B, C, Tx), dtype=torch.float32, device=dev) if need_keys else None
+    gq = torch.empty((B, C, Ty), dtype=torch.float32, device=dev) if need_queries else None
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = _bwd_workspaces.get(dev, lib.aligner_softattn_backward_workspace_bytes(B, C, Tx, Ty))
+        _lib.check(lib.aligner_softattn_backward_f32(
+            k.data_ptr(), q.data_ptr(), None if t_x is None else t_x.data_ptr(), None if prior is None else prior.data_ptr(),
+            gl.data_ptr(), None if gs is None else gs.data_ptr(), None if gk is None else gk.data_ptr(),
+            None if gq is None else gq.data_ptr(), ws.data_ptr(), ws.numel(), B, C, Tx, Ty, float(temperature), simc,
+            _stream(dev)))
+    return gk, gq
+
+
+class _SoftAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, keys_enc, queries_enc, t_x, prior, temperature, sim, want_soft, logp_dtype, pitched):
+        ctx.set_materialize_grads(False)
+        k, q = _chk(keys_enc, "keys_enc"), _chk(queries_enc, "queries_enc")
+        if prior is not None:
+            prior = _chk(prior, "prior")
+        logp, soft = _soft_attention(k, q, t_x, prior, temperature, sim, want_soft, None, logp_dtype, pitched)
+        ctx.temperature, ctx.sim = temperature, sim
+        ctx.dtypes = (keys_enc.dtype, queries_enc.dtype)
+        ctx.save_for_backward(k, q, t_x if isinstance(t_x, torch.Tensor) else None, prior)
+        return logp, soft
+
+    @staticmethod
+    def backward(ctx, g_logp, g_soft):
+        nk, nq = ctx.needs_input_grad[:2]
+        if (g_logp is None and g_soft is None) or not (nk or nq):
+            return (None,) * 9
+        k, q, t_x, prior = ctx.saved_tensors
+        if g_logp is None:
+            g_logp = torch.zeros((k.shape[0], k.shape[2], q.shape[2]), dtype=torch.float32, device=k.device)
+        gk, gq = soft_attention_backward(k, q, g_logp, t_x=t_x, prior=prior, temperature=ctx.temperature, sim=ctx.sim,
+                                         grad_soft=g_soft, need_keys=nk, need_queries=nq)
+        dk, dq = ctx.dtypes
+        return (None if gk is None else gk.to(dk), None if gq is None else gq.to(dq)) + (None,) * 7
 
 
 def pitched_logp(B: int, T_text: int, T_mel: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -190,7 +388,12 @@ class AlignmentEncoderParams:
 def encode(x: torch.Tensor, stack: List[Tuple[torch.Tensor, torch.Tensor]]) -> torch.Tensor:
     """A conv stack (ReLU between the layers) -- in ONE call of the C ABI when every layer has a GEMM form
     (aligner_conv_stack_f32: the input is split once, every k = 1 layer reads the split image its producer wrote; no fp32
-    round trip between layers), layer by layer otherwise."""
+    round trip between layers), layer by layer otherwise.  With grad (x or a weight / bias requires grad) always layer by
+    layer through the differentiable conv1d(), which keeps each layer's input and output for the backward."""
+    if _needs_grad(x, *[t for wb in stack for t in wb]):
+        for n, (w, b) in enumerate(stack):
+            x = conv1d(x, w, b, relu=(n + 1 < len(stack)))
+        return x
     _lib.require_gpu()
     lib = _lib.load()
     x = _chk(x, "x")
@@ -225,7 +428,8 @@ def encode(x: torch.Tensor, stack: List[Tuple[torch.Tensor, torch.Tensor]]) -> t
 def alignment_encoder(text_emb: torch.Tensor, mel: torch.Tensor, params: AlignmentEncoderParams,
                       t_x: Optional[torch.Tensor] = None, prior: Optional[torch.Tensor] = None,
                       want_soft: bool = False, pitched: bool = False):
-    """text_emb [B,C_text,T_text], mel [B,C_mel,T_mel] -> (logp [B,T_text,T_mel], soft or None).  pitched: see soft_attention()."""
+    """text_emb [B,C_text,T_text], mel [B,C_mel,T_mel] -> (logp [B,T_text,T_mel], soft or None).  pitched: see soft_attention().
+    Differentiable in the inputs and every weight / bias of `params` that requires grad (encode(), soft_attention())."""
     k = encode(text_emb, params.key_proj)
     q = encode(mel, params.query_proj)
     return soft_attention(k, q, t_x=t_x, prior=prior, temperature=params.temperature, want_soft=want_soft, pitched=pitched)

@@ -36,7 +36,10 @@ extern "C" {
  *    are what the *_bytes functions of THIS version return: size every buffer with them, never with constants;
  *    new entry points aligner_softattn_ld / aligner_maxpath_ld (a row pitch for the pipeline's own intermediate) and the
  *    test flag ALIGNER_F_TEST_IMPATIENT_FIRST_HALF.
- * 5: the convolution on raw (unprepared) weights left the library: prepare the weights once. */
+ * 5: the convolution on raw (unprepared) weights left the library: prepare the weights once.
+ *    Added within 5 (additive, nothing existing changed): the backward of the front end --
+ *    aligner_softattn_backward_f32 / aligner_softattn_backward_workspace_bytes, aligner_conv1d_prepare_transposed_f32,
+ *    aligner_conv1d_backward_weight_f32 / aligner_conv1d_backward_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -311,6 +314,25 @@ int aligner_softattn_ld(const float *keys_dev, const float *queries_dev,
                         float temperature, int sim, void *stream);
 
 /*
+ * Backward of aligner_softattn_f32.  Given grad_logp_dev = dL/dlogp and (optional) grad_soft_dev = dL/dsoft, [B,Tx,Ty]
+ * fp32, contiguous, and the forward's own keys / queries / t_xs / prior / temperature / sim:
+ *   G      = G_l + soft (G_s - sum_i soft G_s)     (sums over the valid rows i < t_x)
+ *   dlogit = G - softmax_i(logit) sum_i G          (0 on rows i >= t_x)
+ *   L2 : dK[c,i] = 2T (sum_j dlogit q[c,j] - k[c,i] sum_j dlogit)   dQ[c,j] = 2T (sum_i dlogit k[c,i] - q[c,j] sum_i dlogit)
+ *   dot: dK[c,i] =  T  sum_j dlogit q[c,j]                          dQ[c,j] =  T  sum_i dlogit k[c,i]
+ * grad_keys_out_dev [B,C,Tx], grad_queries_out_dev [B,C,Ty]: either may be NULL, not both.  The prior gets no gradient.
+ * t_xs_dev, prior_dev, grad_soft_dev may be NULL.  Masked rows get dK = 0 exactly; an utterance with t_x <= 0 gets zeros.
+ * The logits are recomputed (fp32 products); the result is the same bits on every call (no atomics).
+ * C <= 256 and Tx <= 512 (ALIGNER_EDOM beyond); workspace aligner_softattn_backward_workspace_bytes(B,C,Tx,Ty) bytes.
+ */
+size_t aligner_softattn_backward_workspace_bytes(int B, int C, int Tx, int Ty);
+int aligner_softattn_backward_f32(const float *keys_dev, const float *queries_dev, const int32_t *t_xs_dev,
+                                  const float *prior_dev, const float *grad_logp_dev, const float *grad_soft_dev,
+                                  float *grad_keys_out_dev, float *grad_queries_out_dev,
+                                  void *workspace_dev, size_t workspace_bytes,
+                                  int B, int C, int Tx, int Ty, float temperature, int sim, void *stream);
+
+/*
  * y[b,o,t] = act( bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2] ), zero padded
  * ("same"), K odd; the 1-D conv of the text / mel encoders. relu: 0 or 1.
  * Weights prepared once (split into bf16 halves, in the matrix cores'
@@ -352,6 +374,26 @@ typedef struct aligner_conv_layer {
 size_t aligner_conv_stack_workspace_bytes(const aligner_conv_layer *layers, int n_layers, int B, int T);
 int aligner_conv_stack_f32(const float *x_dev, const aligner_conv_layer *layers, int n_layers, float *y_dev,
                            void *workspace_dev, size_t workspace_bytes, int B, int T, void *stream);
+
+/*
+ * Backward of y = act(conv1d(x, w, b)) (act: ReLU when relu = 1, none when 0):
+ *   dYpre = dY [y > 0] (dY when relu = 0), db[o] = sum_{b,t} dYpre[b,o,t], dW[o,i,k] = sum_{b,t} dYpre[b,o,t] x[b,i,t+k-K/2]
+ *   dX = conv1d(dYpre, w') with w'[i,o,k] = w[o,i,K-1-k]: aligner_conv1d_prepare_transposed_f32 writes the prepared image
+ *   of w' straight from w [Cout,Cin,K] (aligner_conv1d_prepared_bytes(Cin, Cout, K) bytes), then
+ *   aligner_conv1d_prepared_ws_f32(dYpre, image, NULL bias, dX, ..., Cin = Cout, Cout = Cin, K, relu = 0).
+ * aligner_conv1d_backward_weight_f32: x_dev [B,Cin,T], y_dev [B,Cout,T] (relu = 1 only; may be NULL otherwise),
+ *   grad_y_dev [B,Cout,T]; outputs, each nullable but not all: grad_ypre_out_dev [B,Cout,T] (dYpre, for the dX call),
+ *   grad_w_out_dev [Cout,Cin,K], grad_b_out_dev [Cout].  fp32 products, the reduction split over workgroups and summed in
+ *   a fixed order (the same bits on every call); workspace aligner_conv1d_backward_workspace_bytes(B,Cin,Cout,T,K) bytes
+ *   (not needed when only grad_ypre_out_dev is asked for).
+ */
+int aligner_conv1d_prepare_transposed_f32(const float *w_dev, void *prepared_dev, size_t prepared_bytes,
+                                          int Cout, int Cin, int K, void *stream);
+size_t aligner_conv1d_backward_workspace_bytes(int B, int Cin, int Cout, int T, int K);
+int aligner_conv1d_backward_weight_f32(const float *x_dev, const float *y_dev, const float *grad_y_dev,
+                                       float *grad_ypre_out_dev, float *grad_w_out_dev, float *grad_b_out_dev,
+                                       void *workspace_dev, size_t workspace_bytes,
+                                       int B, int Cin, int Cout, int T, int K, int relu, void *stream);
 
 /* ---- the callers either side of the path (build-defined specs) ---- */
 
