@@ -23,6 +23,20 @@ def _rel_err(got, ref):
     return (got - ref).abs().max().item() / (scale if scale > 0 else 1.0)
 
 
+def _rel_err_per_utterance(got, ref, lengths=None):
+    """_rel_err of every batch element against that element's OWN max|ref| (a list of B figures): a wrong gradient of one
+    short utterance does not hide under its neighbours' scale.  lengths: the utterances' text lengths.  With fewer than two
+    text rows the log-softmax over the text is constant, the true gradient identically zero and there is no scale of its
+    own: such an utterance is held to the batch's largest (to 1 if that is zero too)."""
+    got = got.detach().double().to(ref.device)
+    err = (got - ref).abs().flatten(1).max(dim=1).values
+    scale = ref.abs().flatten(1).max(dim=1).values
+    if lengths is not None:
+        scale = torch.where(lengths.to(ref.device) < 2, scale.max().expand_as(scale), scale)
+    scale = torch.where(scale > 0, scale, torch.ones_like(scale))
+    return (err / scale).tolist()
+
+
 def _ref_soft_attention(k, q, t_x=None, prior=None, temperature=0.0005, sim="l2"):
     """oracle/softattn_oracle.soft_attention in float64 (|q|^2 + |k|^2 - 2 k.q: no [B,C,Tx,Ty] temporary)."""
     if sim == "l2":
@@ -94,6 +108,10 @@ def test_soft_attention_gradients_match_float64_autograd(dev, B, C, Tx, Ty, sim,
     assert torch.isfinite(gk).all() and torch.isfinite(gq).all()
     ek, eq = _rel_err(gk, rk), _rel_err(gq, rq)
     assert ek <= REL and eq <= REL, (ek, eq)
+    if B == 64:         # the bench shape: every utterance at its own scale as well
+        pk, pq = _rel_err_per_utterance(gk, rk, t_x), _rel_err_per_utterance(gq, rq, t_x)
+        print(f"softattn backward [64,80,200,1000] ragged={ragged}: per-utterance rel err dK {max(pk):.2e} dQ {max(pq):.2e}")
+        assert max(pk) <= REL and max(pq) <= REL, (pk.index(max(pk)), max(pk), pq.index(max(pq)), max(pq))
 
 
 def test_soft_attention_backward_edges(dev):
@@ -207,6 +225,55 @@ def test_training_step_end_to_end(dev):
     for (w, b), (wr, br) in zip(params.key_proj + params.query_proj, leaves):
         assert w.grad is not None and b.grad is not None
         assert _rel_err(w.grad, wr.grad) <= 1e-3 and _rel_err(b.grad, br.grad) <= 1e-3
+
+
+def test_training_step_at_real_widths(dev):
+    """The same step with the encoders' real widths (512 text, 80 mel, 80 attention channels), B = 8, ragged t_x <= 60 and
+    t_y <= 300: the weight-gradient kernel then walks several chunks a split (80 units on the mel layers; 16 units over 6
+    splits on the 512 -> 1024 text layer), where the small step above gives it one.  Same CTC-form loss, same float64
+    pipeline, same 1e-3 of each tensor's max, for every weight and bias and for text.grad and mel.grad.
+    As above the attention must not be near-uniform (the last layers' bias gradients would cancel to ~1/50 of their weights'
+    at inputs of unit scale and temperature 0.0005, and their relative error would be the fp32 forward's): inputs of a few
+    units and temperature 0.01, and the float64 reference is asserted to give every bias gradient a max of at least a tenth
+    of its weight's (it gives 0.16 to 0.60), so the relative bound means something for each tensor."""
+    import aligner_amd
+    params = aligner_amd.AlignmentEncoderParams.random(512, 80, 80, dev, seed=5)
+    params.temperature = 0.01
+    for w, b in params.key_proj + params.query_proj:
+        w.requires_grad_()
+        b.requires_grad_()
+    g = torch.Generator().manual_seed(6)
+    text = (torch.randn(8, 512, 60, generator=g) * 3.0).to(dev).requires_grad_()
+    mel = (torch.randn(8, 80, 300, generator=g) * 3.0).to(dev).requires_grad_()
+    t_x = torch.tensor([60, 13, 47, 32, 60, 5, 33, 59], dtype=torch.int32, device=dev)
+    t_y = torch.tensor([300, 70, 255, 160, 289, 64, 200, 300], dtype=torch.int32, device=dev)
+    logp, _ = aligner_amd.alignment_encoder(text, mel, params, t_x=t_x)
+    loss = aligner_amd.forward_sum_loss(logp, t_x, t_y, blank_logprob=-1.0)
+    loss.backward()
+    torch.cuda.synchronize()
+    leaves = [(w.detach().double().requires_grad_(), b.detach().double().requires_grad_()) for w, b in params.key_proj + params.query_proj]
+    nk = len(params.key_proj)
+    tr = text.detach().double().requires_grad_()
+    mr = mel.detach().double().requires_grad_()
+
+    def enc(x, stack):
+        for n, (w, b) in enumerate(stack):
+            x = F.conv1d(x, w, b, padding=w.shape[-1] // 2)
+            x = torch.relu(x) if n + 1 < len(stack) else x
+        return x
+    lp, _ = _ref_soft_attention(enc(tr, leaves[:nk]), enc(mr, leaves[nk:]), t_x, None, params.temperature)
+    want = _ctc_mean_loss_f64(lp, t_x.cpu(), t_y.cpu())
+    want.backward()
+    for wr, br in leaves:
+        assert br.grad.abs().max().item() >= 0.1 * wr.grad.abs().max().item() > 0
+    assert tr.grad.abs().max().item() > 0 and mr.grad.abs().max().item() > 0
+    errs = {"loss": abs(loss.item() - want.item()) / abs(want.item()), "text": _rel_err(text.grad, tr.grad),
+            "mel": _rel_err(mel.grad, mr.grad)}
+    for n, ((w, b), (wr, br)) in enumerate(zip(params.key_proj + params.query_proj, leaves)):
+        assert w.grad is not None and b.grad is not None
+        errs[f"w{n}"], errs[f"b{n}"] = _rel_err(w.grad, wr.grad), _rel_err(b.grad, br.grad)
+    print("training step at real widths: rel err " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert max(errs.values()) <= 1e-3, errs
 
 
 def test_no_grad_path_is_unchanged(dev):
