@@ -48,6 +48,32 @@ constexpr int FS_RB = 8;                          // frames between re-basings (
 constexpr int FS_THREADS = 256;                   // wave 0 sweeps, waves 1..3 stage tiles
 constexpr int FS_STAGERS = FS_THREADS - 64;
 constexpr int SY_NW_MAX = 8;                      // ... offsets in the workspace: one per (wave, frame)
+// The systolic kernels' drift estimate (bits per frame, per wave) never exceeds this.  The column maximum of the WHOLE text
+// cannot grow faster than max(logp) + 1 bit a frame; one wave's can, while mass flows in from its neighbour, but that growth
+// ends from one frame to the next and a drift that had followed it would then be wrong by all of it for a tile (fs_rebase).
+constexpr float FS_DRIFT_MAX = 8.0f;
+
+// Re-basing of one wave of the systolic kernels: `mx` is the wave's column maximum after RB frames at `drift`.  Normally
+// the wave re-bases on mx and learns the drift.  The exception is a posterior ridge about to cross into this wave from
+// its neighbour (has: there is one): the neighbour's boundary row -- g0, g1: its last two values of this tile, on the
+// NEIGHBOUR's offset, i.e. relative to the neighbour's own maximum -- then climbs towards that maximum by hundreds of
+// bits a frame, and so does everything in this wave, all of it negligible mass until the ridge is there.  Re-based on
+// its own maximum the wave would meet the ridge up to RB x that rate above 0 and carry it there, where a float32
+// resolves 1e-3, to the end of the tile; a drift that had followed the climb would carry it as far the other way for
+// one more tile (sharp diagonal attention on near-square shapes lost 3e-3 of the loss: tests/test_forward_sum_inputs.py,
+// diag_w3_d150).  So when the boundary row is still more than 64 bits below the neighbour's maximum but will be level
+// within two tiles at its present rate, the wave takes the neighbour's zero level (lvl, on this wave's offset) and
+// drift (sdr): the ridge arrives near 0 and finds the right drift.  A boundary row that keeps its distance (collapsed
+// attention: the neighbour's maximum never flows in) leaves the wave on its own maximum.  Returns the new drift.
+__device__ __forceinline__ float fs_rebase(float &mx, float drift, int RB, bool has, float lvl, float sdr, float g1, float g0) {
+    if (mx < 0.5f * FS_NEG) mx = 0.f;                 // an all-"log 0" column
+    const float gap = -g1, rate = g1 - g0;
+    if (has && g0 > 0.5f * FS_NEG && mx < lvl && gap > 64.0f && gap < 2.0f * RB * rate) {
+        mx = lvl;
+        return sdr;
+    }
+    return fminf(drift + mx * (1.0f / RB), FS_DRIFT_MAX);
+}
 
 struct FwdSumParams {
     const float *logp;      // [B,Tx,Ty]
@@ -78,6 +104,16 @@ __device__ __forceinline__ float fs_in(float lp) { return fmaxf(lp * FS_LOG2E, F
 // FS_NEG_NAT (x log2 e = FS_NEG), rows past the text exactly that
 constexpr float FS_NEG_NAT = -6.9314718e29f;
 __device__ __forceinline__ float fs_nat(float lp) { return fmaxf(lp, FS_NEG_NAT); }
+
+// The plain form's log2 Z and loss leave the forward sweep here.  Every path of the utterance crossing a log-0 cell (a
+// frame whose valid rows are all -inf, say) leaves alpha[tx-1,ty-1] at ~FS_NEG: that is "no alignment", the result
+// t_x > t_y gives -- loss +inf, log Z -inf -- and the gradient makers (fs_has_alignment) then write zeros.
+__device__ __forceinline__ void fs_store_logz(const FwdSumParams &p, int b, double lz) {
+    const bool none = lz < 0.5 * (double)FS_NEG;
+    p.logz[b] = none ? (double)FS_NEG_INF : lz;
+    p.loss[b] = none ? -FS_NEG_INF : (float)(-lz * FS_LN2);
+}
+__device__ __forceinline__ bool fs_has_alignment(double logz) { return logz > (double)FS_NEG_INF; }
 
 // workgroup barrier for LDS traffic only: __syncthreads() would also wait for the stagers' global
 // stores (vmcnt(0)), a memory round trip per tile
@@ -485,8 +521,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_forward_kernel(FwdSumParams
                     for (int j = 0; j < R; ++j)
                         if (R * lane + j == tx - 1) {
                             const double lz = (double)a[j] + C;                     // log2 Z
-                            p.logz[b] = lz;
-                            p.loss[b] = (float)(-lz * FS_LN2);
+                            fs_store_logz(p, b, lz);
                         }
                 }
                 if ((c & (FS_RB - 1)) == FS_RB - 1) {
@@ -521,14 +556,14 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_backward_kernel(FwdSumParam
     int tx = p.t_xs[b], ty = p.t_ys[b];
     tx = tx > p.Tx ? p.Tx : tx;
     ty = ty > p.Ty ? p.Ty : ty;
-    const bool ok = tx >= 1 && tx <= ty;
+    const double logz = p.logz[b];                // (-inf: no alignment, by the lengths or by the log-probs)
+    const bool ok = tx >= 1 && tx <= ty && fs_has_alignment(logz);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     const int ntl = ok ? (ty + TW - 1) / TW : 0;
     // frames past the utterance's last tile (everything when no alignment exists): gradient 0
     for (int r = 0; r < p.Tx; ++r)
         for (int y = ntl * TW + tid; y < p.Ty; y += FS_THREADS) p.grad[ubase + (size_t)r * p.Ty + y] = 0.f;
     if (!ok) return;
-    const double logz = p.logz[b];
     float g_prev[R];                              // beta[x,y+1] + logp[x,y+1], relative to D
 #pragma unroll
     for (int j = 0; j < R; ++j) g_prev[j] = FS_NEG;
@@ -826,16 +861,15 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
                         if (TAIL && y == ty - 1) {                                   // uniform
                             if (row == tx - 1 && !ghost) {
                                 const double lz = (double)a + (Cg + (double)k * (double)drift);   // log2 Z
-                                p.logz[b] = lz;
-                                p.loss[b] = (float)(-lz * FS_LN2);
+                                fs_store_logz(p, b, lz);
                             }
                         }
                         if (k == RB) {
                             // re-base this wave's running column on its maximum and learn the per-frame drift
                             float mx = fs_wave_max_dpp(prev);
-                            if (mx < 0.5f * FS_NEG) mx = 0.f;                        // an all-"log 0" column
+                            const float nd = fs_rebase(mx, drift, RB, w != 0, D0 + (float)RB * dl, sdr[g], rgv[SY_TW - 1], rgv[SY_TW - 2]);
                             Cg += (double)RB * (double)drift + (double)mx;
-                            drift += mx * (1.0f / RB);
+                            drift = nd;
                             prev = fmaxf(prev - mx, FS_NEG);
                         }
                     }
@@ -886,7 +920,10 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
     int tx = p.t_xs[b], ty = p.t_ys[b];
     tx = tx > p.Tx ? p.Tx : tx;
     ty = ty > p.Ty ? p.Ty : ty;
-    const bool ok = tx >= 1 && tx <= ty;
+    // (log Z = -inf: no alignment, by the lengths or by the log-probs.  BETA_ONLY runs beside the forward sweep and cannot
+    // know: it sweeps, and fwdsum_combine_kernel writes the zeros)
+    const double logz = BETA_ONLY ? 0.0 : p.logz[b];
+    const bool ok = tx >= 1 && tx <= ty && fs_has_alignment(logz);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     const int ntl = ok ? (ty + SY_TW - 1) / SY_TW : 0;
     // frames past the utterance's last tile (everything when no alignment exists): gradient 0
@@ -895,7 +932,6 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
         for (int r = 0; r < p.Tx; ++r)
             for (int y = ntl * SY_TW + tid; y < p.Ty; y += SY_THREADS) p.grad[ubase + (size_t)r * p.Ty + y] = 0.f;
     if (!ok) return;
-    const double logz = BETA_ONLY ? 0.0 : p.logz[b];
     const double *offs = p.offs + ((size_t)b * SY_NW_MAX + w) * p.NT;
     double *doffs = p.doffs + ((size_t)b * SY_NW_MAX + w) * p.NT;
     const int row = 63 * w + lane;                            // sweeper: lane 63 is the ghost (row 63w+63)
@@ -1098,9 +1134,9 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
                         g_prev = gn;
                         if (k == RB) {
                             float mx = fs_wave_max_dpp(g_prev);
-                            if (mx < 0.5f * FS_NEG) mx = 0.f;
+                            const float nd = fs_rebase(mx, drift, RB, has, D0 + (float)RB * dl, sdr[g], rgv[0], rgv[1]);
                             Dg += (double)RB * (double)drift + (double)mx;
-                            drift += mx * (1.0f / RB);
+                            drift = nd;
                             g_prev = fmaxf(g_prev - mx, FS_NEG);
                         }
                     }
@@ -1144,7 +1180,7 @@ __device__ __forceinline__ void fwdsum_combine_body(const FwdSumParams &p, const
     int tx = p.t_xs[b], ty = p.t_ys[b];
     tx = tx > p.Tx ? p.Tx : tx;
     ty = ty > p.Ty ? p.Ty : ty;
-    const bool ok = tx >= 1 && tx <= ty;
+    const bool ok = tx >= 1 && tx <= ty && fs_has_alignment(p.logz[b]);
     {
         const int y = yb + tid;
         float v = 0.f, n = 0.f;
@@ -1214,6 +1250,36 @@ __device__ __forceinline__ float fs_lae3(float a, float b, float c) {
     return m + __builtin_amdgcn_logf(__builtin_amdgcn_exp2f(a - m) + __builtin_amdgcn_exp2f(b - m) +
                                      __builtin_amdgcn_exp2f(c - m));
 }
+
+// The one-wave CTC kernels keep their states in float64.  They hold all rows on ONE offset per frame, and the CTC form's
+// posterior often lies thousands of bits below the column maximum (collapsed attention: depth x T_text; scale-8 noise
+// or a jumping ridge over 600 rows: several thousand).  A float32 there resolves 5e-4 bits and every frame's
+// "+ (score - drift)" rounds once -- the same way each time when the addend repeats, as a blank's does -- so 1 000 frames
+// moved the occupancies by up to 13 % (tests/test_forward_sum_inputs.py).  The systolic kernels escape
+// this with one offset per 63-row wave; here the states' sums and the offsets' bookkeeping are done in float64 (full
+// rate on CDNA) and only the log term, which lies in (0, log2 3], is float32.  alpha leaves as float32: one rounding.
+__device__ __forceinline__ double fs_lae2d(double a, double b) {
+    const double m = fmax(a, b);
+    return m + (double)__builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(-fabsf((float)(a - b))));
+}
+__device__ __forceinline__ double fs_lae3d(double a, double b, double c) {
+    const double m = fmax(fmax(a, b), c);
+    return m + (double)__builtin_amdgcn_logf(__builtin_amdgcn_exp2f((float)(a - m)) + __builtin_amdgcn_exp2f((float)(b - m)) +
+                                             __builtin_amdgcn_exp2f((float)(c - m)));
+}
+__device__ __forceinline__ double fs_from_lane_below_d(double edge, double src) {
+    return __hiloint2double(__builtin_bit_cast(int, fs_from_lane_below(__builtin_bit_cast(float, __double2hiint(edge)),
+                                                                       __builtin_bit_cast(float, __double2hiint(src)))),
+                            __builtin_bit_cast(int, fs_from_lane_below(__builtin_bit_cast(float, __double2loint(edge)),
+                                                                       __builtin_bit_cast(float, __double2loint(src)))));
+}
+__device__ __forceinline__ double fs_from_lane_above_d(double edge, double src) {
+    return __hiloint2double(__builtin_bit_cast(int, fs_from_lane_above(__builtin_bit_cast(float, __double2hiint(edge)),
+                                                                       __builtin_bit_cast(float, __double2hiint(src)))),
+                            __builtin_bit_cast(int, fs_from_lane_above(__builtin_bit_cast(float, __double2loint(edge)),
+                                                                       __builtin_bit_cast(float, __double2loint(src)))));
+}
+constexpr double FS_NEG_D = (double)FS_NEG;
 
 struct CtcParams {
     FwdSumParams f;         // logp = the raw scores x; alpha = log2 alpha of the TOKEN states
@@ -1292,10 +1358,10 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_forward_kernel(CtcParam
         return;
     }
     const int ntl = (ty + TW - 1) / TW;
-    float pB[R], pT[R];
+    double pB[R], pT[R];
 #pragma unroll
-    for (int j = 0; j < R; ++j) { pB[j] = FS_NEG; pT[j] = FS_NEG; }
-    if (lane == 0) pB[0] = 0.f;                   // B_0 before the first frame: log 1
+    for (int j = 0; j < R; ++j) { pB[j] = FS_NEG_D; pT[j] = FS_NEG_D; }
+    if (lane == 0) pB[0] = 0.0;                   // B_0 before the first frame: log 1
     float drift = 0.f;
     double C = 0.0, NS = 0.0;                     // NS: sum of the frames' normalisers
     for (int ph = 0; ph < ntl + 2; ++ph) {
@@ -1344,45 +1410,46 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_forward_kernel(CtcParam
                     x[j] = w.x; x[j + 1] = w.y; x[j + 2] = w.z; x[j + 3] = w.w;
                 }
                 NS += (double)tnrm[(t & 1) * TW + c];
-                const float up0 = fs_from_lane_below(FS_NEG, pT[R - 1]);             // T of the row below this lane's first
-                const float bl = q.blank2 - drift;
-                float nB[R], nT[R];
+                const double up0 = fs_from_lane_below_d(FS_NEG_D, pT[R - 1]);        // T of the row below this lane's first
+                const double dr = (double)drift, bl = (double)q.blank2 - dr;
+                double nB[R], nT[R];
 #pragma unroll
                 for (int j = 0; j < R; ++j) {
                     const int row = R * lane + j;
-                    const float upT = j ? pT[j - 1] : up0;
-                    const float vb = fs_lae2(pB[j], upT) + bl;
-                    const float vt = fs_lae3(pT[j], pB[j], upT) + (x[j] - drift);
-                    nB[j] = (row <= tx) ? fmaxf(vb, FS_NEG) : FS_NEG;
-                    nT[j] = (row < tx) ? fmaxf(vt, FS_NEG) : FS_NEG;
+                    const double upT = j ? pT[j - 1] : up0;
+                    const double vb = fs_lae2d(pB[j], upT) + bl;
+                    const double vt = fs_lae3d(pT[j], pB[j], upT) + ((double)x[j] - dr);
+                    nB[j] = (row <= tx) ? fmax(vb, FS_NEG_D) : FS_NEG_D;
+                    nT[j] = (row < tx) ? fmax(vt, FS_NEG_D) : FS_NEG_D;
                 }
                 C += (double)drift;
                 if (lane == 0) toff[(t & 1) * TW + c] = C;
 #pragma unroll
                 for (int j = 0; j < R; j += 4)
-                    *reinterpret_cast<float4 *>(dst + c * ROWS + j) = make_float4(nT[j], nT[j + 1], nT[j + 2], nT[j + 3]);
+                    *reinterpret_cast<float4 *>(dst + c * ROWS + j) =
+                        make_float4((float)nT[j], (float)nT[j + 1], (float)nT[j + 2], (float)nT[j + 3]);
 #pragma unroll
                 for (int j = 0; j < R; ++j) { pB[j] = nB[j]; pT[j] = nT[j]; }
                 if (y == ty - 1) {                                                  // uniform: Z = T_{tx-1} + B_tx
-                    const float upn = fs_from_lane_below(FS_NEG, pT[R - 1]);
+                    const double upn = fs_from_lane_below_d(FS_NEG_D, pT[R - 1]);
 #pragma unroll
                     for (int j = 0; j < R; ++j)
                         if (R * lane + j == tx) {
-                            const double lz = (double)fs_lae2(pB[j], j ? pT[j - 1] : upn) + C;     // log2 Z of the raw scores
+                            const double lz = fs_lae2d(pB[j], j ? pT[j - 1] : upn) + C;            // log2 Z of the raw scores
                             p.logz[b] = lz;
                             p.loss[b] = (float)(-(lz - NS) * FS_LN2);
                         }
                 }
                 if ((c & (FS_RB - 1)) == FS_RB - 1) {
-                    float m = fmaxf(pB[0], pT[0]);
+                    double ml = fmax(pB[0], pT[0]);
 #pragma unroll
-                    for (int j = 1; j < R; ++j) m = fmaxf(m, fmaxf(pB[j], pT[j]));
-                    m = fs_wave_max_dpp(m);
+                    for (int j = 1; j < R; ++j) ml = fmax(ml, fmax(pB[j], pT[j]));
+                    float m = fs_wave_max_dpp((float)ml);                             // (any common float serves as the new zero)
                     if (m < 0.5f * FS_NEG) m = 0.f;
                     C += (double)m;
                     drift += m * (1.0f / FS_RB);
 #pragma unroll
-                    for (int j = 0; j < R; ++j) { pB[j] = fmaxf(pB[j] - m, FS_NEG); pT[j] = fmaxf(pT[j] - m, FS_NEG); }
+                    for (int j = 0; j < R; ++j) { pB[j] = fmax(pB[j] - (double)m, FS_NEG_D); pT[j] = fmax(pT[j] - (double)m, FS_NEG_D); }
                 }
             }
         }
@@ -1412,9 +1479,9 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_backward_kernel(CtcPara
         for (int y = ntl * TW + tid; y < p.Ty; y += FS_THREADS) p.grad[ubase + (size_t)r * p.Ty + y] = 0.f;
     if (!ok) return;
     const double logz = p.logz[b];
-    float gB[R], gT[R];                           // beta + emission of frame y+1, relative to D
+    double gB[R], gT[R];                          // beta + emission of frame y+1, relative to D (float64: see fs_lae2d)
 #pragma unroll
-    for (int j = 0; j < R; ++j) { gB[j] = FS_NEG; gT[j] = FS_NEG; }
+    for (int j = 0; j < R; ++j) { gB[j] = FS_NEG_D; gT[j] = FS_NEG_D; }
     float drift = 0.f;
     double D = 0.0;
     for (int ph = 0; ph < ntl + 2; ++ph) {
@@ -1475,28 +1542,30 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_backward_kernel(CtcPara
                     x[j] = v.x; x[j + 1] = v.y; x[j + 2] = v.z; x[j + 3] = v.w;
                     al[j] = w.x; al[j + 1] = w.y; al[j + 2] = w.z; al[j + 3] = w.w;
                 }
-                const float st = (float)(toff[buf * TW + c] + D - logz);            // uniform
+                const double st = toff[buf * TW + c] + D - logz;                    // uniform
                 const float ny = tnrm[buf * TW + c];
-                const float aB = fs_from_lane_above(FS_NEG, gB[0]);                  // row above this lane's last one
-                const float aT = fs_from_lane_above(FS_NEG, gT[0]);
-                float nB[R], nT[R], gr[R];
+                const double aB = fs_from_lane_above_d(FS_NEG_D, gB[0]);             // row above this lane's last one
+                const double aT = fs_from_lane_above_d(FS_NEG_D, gT[0]);
+                const double dr = (double)drift, bl = (double)q.blank2 - dr;
+                double nB[R], nT[R];
+                float gr[R];
 #pragma unroll
                 for (int j = 0; j < R; ++j) {
                     const int row = R * lane + j;
-                    float bT, bB;
+                    double bT, bB;
                     if (y == ty - 1) {                                               // uniform branch
-                        bT = (row == tx - 1) ? 0.f : FS_NEG;
-                        bB = (row == tx) ? 0.f : FS_NEG;
+                        bT = (row == tx - 1) ? 0.0 : FS_NEG_D;
+                        bB = (row == tx) ? 0.0 : FS_NEG_D;
                     } else {
-                        bT = fs_lae3(gT[j], j + 1 < R ? gB[j + 1] : aB, j + 1 < R ? gT[j + 1] : aT);
-                        bB = fs_lae2(gB[j], gT[j]);
+                        bT = fs_lae3d(gT[j], j + 1 < R ? gB[j + 1] : aB, j + 1 < R ? gT[j + 1] : aT);
+                        bB = fs_lae2d(gB[j], gT[j]);
                     }
-                    if (row >= tx) bT = FS_NEG;
-                    if (row > tx) bB = FS_NEG;
-                    const float occ = __builtin_amdgcn_exp2f(al[j] + bT + st);       // 2^(-1e30) = 0
+                    if (row >= tx) bT = FS_NEG_D;
+                    if (row > tx) bB = FS_NEG_D;
+                    const float occ = __builtin_amdgcn_exp2f((float)((double)al[j] + bT + st));   // 2^(-1e30) = 0
                     gr[j] = (row < tx) ? __builtin_amdgcn_exp2f(x[j] - ny) - occ : 0.f;
-                    nT[j] = fmaxf(bT + (x[j] - drift), FS_NEG);
-                    nB[j] = fmaxf(bB + (q.blank2 - drift), FS_NEG);
+                    nT[j] = fmax(bT + ((double)x[j] - dr), FS_NEG_D);
+                    nB[j] = fmax(bB + bl, FS_NEG_D);
                 }
                 D += (double)drift;
 #pragma unroll
@@ -1505,15 +1574,15 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_backward_kernel(CtcPara
 #pragma unroll
                 for (int j = 0; j < R; ++j) { gB[j] = nB[j]; gT[j] = nT[j]; }
                 if ((c & (FS_RB - 1)) == 0) {
-                    float m = fmaxf(gB[0], gT[0]);
+                    double ml = fmax(gB[0], gT[0]);
 #pragma unroll
-                    for (int j = 1; j < R; ++j) m = fmaxf(m, fmaxf(gB[j], gT[j]));
-                    m = fs_wave_max_dpp(m);
+                    for (int j = 1; j < R; ++j) ml = fmax(ml, fmax(gB[j], gT[j]));
+                    float m = fs_wave_max_dpp((float)ml);
                     if (m < 0.5f * FS_NEG) m = 0.f;
                     D += (double)m;
                     drift += m * (1.0f / FS_RB);
 #pragma unroll
-                    for (int j = 0; j < R; ++j) { gB[j] = fmaxf(gB[j] - m, FS_NEG); gT[j] = fmaxf(gT[j] - m, FS_NEG); }
+                    for (int j = 0; j < R; ++j) { gB[j] = fmax(gB[j] - (double)m, FS_NEG_D); gT[j] = fmax(gT[j] - (double)m, FS_NEG_D); }
                 }
             }
         }
@@ -1680,9 +1749,9 @@ __device__ __forceinline__ void fwdsum_ctc_forward_sys_body(const CtcParams &q, 
             else                 frames(std::true_type{});
             {   // re-base on the column's maximum, learn the per-frame drift
                 float mx = fs_wave_max_dpp(fmaxf(pT, pB));
-                if (mx < 0.5f * FS_NEG) mx = 0.f;
+                const float nd = fs_rebase(mx, drift, RB, w != 0, D0 + (float)RB * dl, sdr, rgv[SY_TW - 1], rgv[SY_TW - 2]);
                 Cg += (double)RB * (double)drift + (double)mx;
-                drift += mx * (1.0f / RB);
+                drift = nd;
                 pT = fmaxf(pT - mx, FS_NEG);
                 pB = fmaxf(pB - mx, FS_NEG);
             }
@@ -1891,9 +1960,9 @@ __device__ __forceinline__ void fwdsum_ctc_backward_sys_body(const CtcParams &q,
             else         frames(std::true_type{});
             {
                 float mx = fs_wave_max_dpp(fmaxf(gT, gB));
-                if (mx < 0.5f * FS_NEG) mx = 0.f;
+                const float nd = fs_rebase(mx, drift, RB, has, D0 + (float)RB * dl, sdr, fmaxf(rgv[0].x, rgv[0].y), fmaxf(rgv[1].x, rgv[1].y));
                 Dg += (double)RB * (double)drift + (double)mx;
-                drift += mx * (1.0f / RB);
+                drift = nd;
                 gT = fmaxf(gT - mx, FS_NEG);
                 gB = fmaxf(gB - mx, FS_NEG);
             }

@@ -405,6 +405,9 @@ int aligner_conv1d_backward_weight_f32(const float *x_dev, const float *y_dev, c
  *   logp_dev [B,Tx,Ty] fp32 (Tx <= 1024), t_xs_dev/t_ys_dev [B] int32, loss_out_dev [B] fp32
  *   (+inf where t_x < 1 or t_x > t_y), grad_out_dev optional [B,Tx,Ty] fp32,
  *   workspace_dev aligner_forward_sum_workspace_bytes(B,Tx,Ty) bytes (the alpha tiles).
+ * -inf log-probs are legal (log 0: a hard mask, the padding rows of soft_attention).  An utterance whose EVERY alignment
+ * crosses such a cell -- log Z below half the kernels' finite "log 0" of -1e30 -- has no alignment either: loss +inf and an
+ * all-zero gradient, exactly as for t_x > t_y; the other utterances of the batch are not affected.
  * With the gradient, batches of at most half the CU count run the alpha and the beta sweep side by side in one launch
  * (beta travels through grad_out_dev) and a combining pass writes the gradient in place; larger batches run forward, then
  * backward.  Same results up to fp32 rounding of the exponent sum (tests/test_objective.py).  T_mel % 4 == 0 and 16-byte
