@@ -15,12 +15,14 @@ import sys
 from .maxpath import Alignment, align, maximum_path, maximum_path_c, read_status  # noqa: F401
 from .softattn import (AlignmentEncoderParams, alignment_encoder, conv1d, conv1d_backward, soft_attention,  # noqa: F401
                        soft_attention_backward)
-from .objective import beta_binomial_prior, forward_sum, forward_sum_loss, regulate  # noqa: F401
+from .objective import (alignment_loss, average_by_duration, beta_binomial_prior, binarization_loss, forward_sum,  # noqa: F401
+                        forward_sum_loss, regulate, segment_reduce)
 from .mobo import BoundarySearch, boundary_search, boundary_search_backward, soft_boundaries  # noqa: F401
 
 __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status",
            "soft_attention", "soft_attention_backward", "conv1d", "conv1d_backward", "alignment_encoder", "AlignmentEncoderParams",
-           "forward_sum", "forward_sum_loss", "beta_binomial_prior", "regulate", "boundary_search", "boundary_search_backward", "soft_boundaries", "BoundarySearch", "install_dropin"]
+           "forward_sum", "forward_sum_loss", "beta_binomial_prior", "regulate", "segment_reduce", "average_by_duration", "binarization_loss", "alignment_loss",
+           "boundary_search", "boundary_search_backward", "soft_boundaries", "BoundarySearch", "install_dropin"]
 
 
 def install_dropin() -> None:

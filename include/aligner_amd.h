@@ -39,7 +39,8 @@ extern "C" {
  * 5: the convolution on raw (unprepared) weights left the library: prepare the weights once.
  *    Added within 5 (additive, nothing existing changed): the backward of the front end --
  *    aligner_softattn_backward_f32 / aligner_softattn_backward_workspace_bytes, aligner_conv1d_prepare_transposed_f32,
- *    aligner_conv1d_backward_weight_f32 / aligner_conv1d_backward_workspace_bytes. */
+ *    aligner_conv1d_backward_weight_f32 / aligner_conv1d_backward_workspace_bytes; and the hard half of the training
+ *    objective -- aligner_segment_reduce_f32, aligner_bin_loss, aligner_bin_loss_grad_f32. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -445,6 +446,52 @@ int aligner_beta_binomial_prior_f32(const int32_t *t_xs_dev, const int32_t *t_ys
  * tok_out_dev optional [B,Ty] int32 (-1 past the end). */
 int aligner_regulate_f32(const float *h_dev, const int32_t *durations_dev, float *out_dev, int32_t *tok_out_dev,
                          int B, int C, int Tx, int Ty, void *stream);
+
+/*
+ * Segment reduction over the durations, frames -> tokens: the inverse direction of the length regulator.  With
+ * s_x = sum(max(durations[b,i],0), i < x) and e_x = s_x + max(durations[b,x],0) -- exactly the segments
+ * aligner_regulate_f32 defines: negative durations count as 0, a sum that runs past Ty is clipped --
+ *   tokens_out[b,c,x] = sum of frames[b,c,y] over y in [s_x, e_x) and [0, Ty)
+ * and with mean != 0 that sum divided by the number of frames actually summed.  A token without a frame gets 0; every
+ * element of tokens_out is written.  mean = 0 is the adjoint of aligner_regulate_f32 (the regulator's gradient with
+ * respect to h: pass the gradient of its output as `frames`); mean = 1 is the per-token averaging of pitch / energy.
+ *   frames_dev [B,C,Ty] fp32, durations_dev [B,Tx] int32, tokens_out_dev [B,C,Tx] fp32; Tx <= 2048 (ALIGNER_EDOM beyond).
+ * Deterministic: a workgroup owns whole (utterance, channel) rows, a wave sums a row's frames in one fixed order
+ * (segmented scan over the lanes, per-token accumulators in LDS), no atomics -- the same bits on every run, and a run
+ * time that does not depend on how the frames are distributed over the tokens.  Ty % 4 == 0 and a 16-byte aligned
+ * frames pointer take the 16-byte loads.
+ */
+int aligner_segment_reduce_f32(const float *frames_dev, const int32_t *durations_dev, float *tokens_out_dev,
+                               int B, int C, int Tx, int Ty, int mean, void *stream);
+
+/*
+ * Binarization loss of the OTA aligner: minus the summed log soft-probability at the cells of the hard path (the
+ * published form is log(clamp(soft, 1e-12)) at the path's cells, averaged over them; neither the reference snapshot
+ * nor SNIPPETS.md holds that code: parity unpinned, like the other OTA pieces).
+ * A frame (b,y) counts when 0 <= tok[b,y] < Tx and, with t_ys_dev given, y < t_ys[b].
+ *   nll_out[b]   = -sum over the counting frames of max(logp[b, tok[b,y], y], min_logp)
+ *   count_out[b] = number of counting frames
+ * A cell below min_logp (-inf and NaN included) contributes min_logp to the loss and nothing to the gradient.
+ *   logp_dev [B,Tx,*] of logp_dtype F32, BF16 or F16 at a row pitch of ld_logp >= Ty elements (as aligner_maxpath_ld:
+ *   the pipeline's pitched log-probs are read in place); tok_dev [B,Ty] int32 as aligner_maxpath / aligner_regulate_f32
+ *   write it; t_ys_dev optional [B] int32; nll_out_dev [B] fp32; count_out_dev [B] int32; Tx <= 2048 (ALIGNER_EDOM).
+ * One workgroup per utterance and a fixed summation order: deterministic.
+ */
+int aligner_bin_loss(const void *logp_dev, int logp_dtype, int ld_logp, const int32_t *tok_dev,
+                     const int32_t *t_ys_dev, float min_logp, float *nll_out_dev, int32_t *count_out_dev,
+                     int B, int Tx, int Ty, void *stream);
+
+/*
+ * Its gradient, d sum_b(scale[b] * nll[b]) / d logp: -scale[b] at every counting cell with logp > min_logp, 0 elsewhere.
+ *   scale_dev [B] fp32 on the device (so a normaliser such as 1 / sum(count) never visits the host);
+ *   grad_dev [B,Tx,Ty] fp32, contiguous.
+ * accumulate = 0: the whole tensor is written (+0 off the path).  accumulate = 1: -scale[b] is added to those cells
+ * and nothing else is touched -- the way to put the binarization term into a gradient that is already there
+ * (aligner_forward_sum_ctc_f32's) without a zero-fill or a dense add.
+ */
+int aligner_bin_loss_grad_f32(const void *logp_dev, int logp_dtype, int ld_logp, const int32_t *tok_dev,
+                              const int32_t *t_ys_dev, float min_logp, const float *scale_dev, float *grad_dev,
+                              int accumulate, int B, int Tx, int Ty, void *stream);
 
 /*
  * MoBoAligner monotonic boundary search (BASELINE config 5; build-defined spec from the paper the reference

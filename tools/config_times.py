@@ -95,3 +95,8 @@ for name, m in (("full-length mask", full), ("ragged mask", mask)):
     for _ in range(200): aligner_amd.maximum_path(v, m)
     t_host = (time.perf_counter() - t0) / 200 * 1e6; torch.cuda.synchronize()
     print("drop-in maximum_path(value, mask) [64,200,1000], %s: %.1f us of GPU time per call, %.1f us wall per synchronous call, %.1f us of host time per asynchronous call" % (name, t_gpu, t_wall, t_host))
+
+# the hard half of the objective: segment reduction, binarization loss, alignment_loss (tools/hard_objective_times.py)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hard_objective_times
+hard_objective_times.main()
