@@ -40,7 +40,8 @@ extern "C" {
  *    Added within 5 (additive, nothing existing changed): the backward of the front end --
  *    aligner_softattn_backward_f32 / aligner_softattn_backward_workspace_bytes, aligner_conv1d_prepare_transposed_f32,
  *    aligner_conv1d_backward_weight_f32 / aligner_conv1d_backward_workspace_bytes; and the hard half of the training
- *    objective -- aligner_segment_reduce_f32, aligner_bin_loss, aligner_bin_loss_grad_f32. */
+ *    objective -- aligner_segment_reduce_f32, aligner_bin_loss, aligner_bin_loss_grad_f32; and the hard search with
+ *    optional pauses between tokens -- aligner_pausepath / aligner_pausepath_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -492,6 +493,44 @@ int aligner_bin_loss(const void *logp_dev, int logp_dtype, int ld_logp, const in
 int aligner_bin_loss_grad_f32(const void *logp_dev, int logp_dtype, int ld_logp, const int32_t *tok_dev,
                               const int32_t *t_ys_dev, float min_logp, const float *scale_dev, float *grad_dev,
                               int accumulate, int B, int Tx, int Ty, void *stream);
+
+/*
+ * Hard alignment search with optional pauses between tokens: the Viterbi path over the CTC topology of the token
+ * sequence, the decoding counterpart of aligner_forward_sum_ctc_f32's blank (build-defined spec: neither the reference
+ * snapshot nor SNIPPETS.md holds code for it; stated in full in csrc/pausepath.hip and tests/pausepath_oracle.py).
+ * States s = 0 .. 2 t_x per utterance: s = 2g is the pause in gap g (the place before token g; gap 0 leads, gap t_x
+ * trails) and scores pause[y] on frame y, s = 2x+1 is token x and scores value[x,y].  A token takes at least one frame,
+ * a pause zero or more; a path moves from a state to itself, to the next state, or from a token straight to the next
+ * token.  Arithmetic is fp32, one add per cell; among the predecessors that exist (stay, advance, skip -- in this order)
+ * a later one replaces an earlier one only when strictly greater, so ties keep the earlier and a NaN never wins; the path
+ * ends in the last token unless the trailing pause exists on the last frame and is strictly greater.  Predecessors
+ * outside the band are excluded, not scored: the result is a legal path (monotone, every token at least one frame,
+ * durations summing to t_y) for any scores, -inf and NaN included.
+ *   value_dev [B,Tx,*] of value_dtype F32, BF16 or F16 at a row pitch of ld_value >= Ty elements (read in place)
+ *   pause_dev optional [B,Ty] fp32 pause score per frame; NULL: pause_score on every frame
+ *   gap_mask_dev optional [B,Tx+1] uint8: a gap whose entry is 0 holds no pause; NULL: every gap may
+ *   t_xs_dev, t_ys_dev [B] int32
+ * Outputs, each optional, at least one; every element of a requested one is written:
+ *   tok_out [B,Ty] int32: x on a frame of token x, -2-g on a pause frame of gap g, -1 for y >= t_y (negative means
+ *                 "no token": aligner_bin_loss skips such frames)
+ *   durations_out [B,Tx] int32 frames per token; pauses_out [B,Tx+1] int32 frames per gap
+ *   state_durations_out [B,2*Tx+1] int32: the same numbers interleaved (even entries gaps, odd entries tokens) -- what
+ *                 aligner_regulate_f32 takes for text encodings interleaved with a pause embedding
+ *   score_out [B] fp32: the path's running score on its last frame
+ * An utterance with t_x < 1, t_y < 1, t_x > t_y or a length outside [0,Tx] / [0,Ty] has no path: durations and pauses
+ * 0, tok -1, score -inf; the others of the batch are unaffected.
+ * One launch (sweep, backtrack and outputs), one workgroup per utterance, no atomics: deterministic.  Tx <= 1024
+ * (ALIGNER_EDOM beyond).  The workspace holds decision words only, for shapes whose words do not fit LDS:
+ * aligner_pausepath_workspace_bytes(B,Tx,Ty) bytes, 0 when they fit -- and 0 for a shape that is not supported.  Both
+ * functions decide "fits" against gfx950's 160 KiB of LDS per workgroup, so a caller who is told 0 bytes is never asked
+ * for more; on a device that gives a workgroup less than the launch needs the call fails with ALIGNER_EDOM.
+ */
+size_t aligner_pausepath_workspace_bytes(int B, int Tx, int Ty);
+int aligner_pausepath(const void *value_dev, int value_dtype, int ld_value, const float *pause_dev, float pause_score,
+                      const uint8_t *gap_mask_dev, const int32_t *t_xs_dev, const int32_t *t_ys_dev,
+                      int32_t *tok_out_dev, int32_t *durations_out_dev, int32_t *pauses_out_dev,
+                      int32_t *state_durations_out_dev, float *score_out_dev,
+                      void *workspace_dev, size_t workspace_bytes, int B, int Tx, int Ty, void *stream);
 
 /*
  * MoBoAligner monotonic boundary search (BASELINE config 5; build-defined spec from the paper the reference
