@@ -41,7 +41,8 @@ extern "C" {
  *    aligner_softattn_backward_f32 / aligner_softattn_backward_workspace_bytes, aligner_conv1d_prepare_transposed_f32,
  *    aligner_conv1d_backward_weight_f32 / aligner_conv1d_backward_workspace_bytes; and the hard half of the training
  *    objective -- aligner_segment_reduce_f32, aligner_bin_loss, aligner_bin_loss_grad_f32; and the hard search with
- *    optional pauses between tokens -- aligner_pausepath / aligner_pausepath_workspace_bytes. */
+ *    optional pauses between tokens -- aligner_pausepath / aligner_pausepath_workspace_bytes; and the Glow-TTS / VITS
+ *    log-likelihood front end -- aligner_gauss_logp / aligner_gauss_logp_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -333,6 +334,41 @@ int aligner_softattn_backward_f32(const float *keys_dev, const float *queries_de
                                   float *grad_keys_out_dev, float *grad_queries_out_dev,
                                   void *workspace_dev, size_t workspace_bytes,
                                   int B, int C, int Tx, int Ty, float temperature, int sim, void *stream);
+
+/* ---- Glow-TTS / VITS log-likelihood front end --------------------------- */
+
+/*
+ * The `value` tensor Glow-TTS and VITS hand to monotonic_align.maximum_path: the log-density of every latent frame under
+ * every token's diagonal Gaussian,
+ *   value[b,i,j] = sum_c ( -1/2 ln 2pi - logstd[b,c,i] - 1/2 (z[b,c,j] - mean[b,c,i])^2 exp(-2 logstd[b,c,i]) )
+ *   z_dev       [B,C,Ty] fp32  the flow's output    (channel-major, as both models hold it)
+ *   mean_dev    [B,C,Tx] fp32  the text encoder's mean
+ *   logstd_dev  [B,C,Tx] fp32  its log standard deviation
+ *   t_xs_dev, t_ys_dev  optional [B] int32 lengths; NULL = the full extent (Tx / Ty)
+ *   value_out_dev  element [b,i,j] at ((b*Tx + i)*ld_value + j), of value_dtype F32, or BF16 as the round-to-nearest-even
+ *               of the fp32 result (aligner_maxpath / aligner_maxpath_ld read either as it is).  ld_value == Ty
+ *               (contiguous), or a row pitch ld_value > Ty with rows on 16-byte boundaries -- the pipeline's own
+ *               intermediate in front of aligner_maxpath_ld.  Only the columns < Ty are written.
+ *   workspace_dev  aligner_gauss_logp_workspace_bytes(B,C,Tx) bytes (0 for a shape that is not supported): the [Tx,2C]
+ *               operand (exp(-2 logstd), mean exp(-2 logstd)) split to bf16 halves in MFMA fragment order and the
+ *               per-token constant, prepared once per call.
+ * Masked cells: a cell with i >= t_x[b] or j >= t_y[b] is written as 0.0 -- what Glow-TTS's `logp * attn_mask` and the
+ * reference's `value * mask` hold there; an utterance with t_x <= 0 or t_y <= 0 is all zeros.
+ * Arithmetic: the sum is expanded into one contraction of depth 2C plus a per-token constant and runs on the bf16 matrix
+ * cores with every fp32 operand split in two bf16 halves (hi*hi + hi*lo + lo*hi, fp32 accumulate: ~2^-16 relative per
+ * product).  The expanded terms cancel where z ~ mean and the deviation is small, so the error is relative to the
+ * magnitude of what is summed, S = sum_c (1/2 z^2 w + |z mean| w + 1/2 mean^2 w + |logstd| + 1/2 ln 2pi), w = exp(-2
+ * logstd): |value - exact| <= 2^-14 S.  No atomics: the same bits on every call.  No gradient.
+ * Domain: 1 <= C <= 256 (any C: the contraction is padded with zeros inside the kernel), Tx <= 1024, any Ty, B <= 65535,
+ * Tx*ld_value < 2^29: ALIGNER_EDOM beyond; ALIGNER_EINVAL for a null pointer, a shape below 1, ld_value < Ty or a dtype
+ * other than F32 / BF16.  Arguments are validated before any HIP call.  Two launches (prepare, main), asynchronous.
+ */
+size_t aligner_gauss_logp_workspace_bytes(int B, int C, int Tx);
+int aligner_gauss_logp(const float *z_dev, const float *mean_dev, const float *logstd_dev,
+                       const int32_t *t_xs_dev, const int32_t *t_ys_dev,
+                       void *value_out_dev, int value_dtype, int ld_value,
+                       void *workspace_dev, size_t workspace_bytes,
+                       int B, int C, int Tx, int Ty, void *stream);
 
 /*
  * y[b,o,t] = act( bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2] ), zero padded
