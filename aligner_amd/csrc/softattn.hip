@@ -550,7 +550,9 @@ __global__ __launch_bounds__(SA_THREADS, (KS == 16 && MULTI) ? 1 : 2) void softa
         const float m_fin = (m_all == NEG_INF_F) ? 0.f : m_all;
         const float l_all = (m == NEG_INF_F ? 0.f : l * __builtin_amdgcn_exp2f(m - m_fin)) +
                             (m_o == NEG_INF_F ? 0.f : l_o * __builtin_amdgcn_exp2f(m_o - m_fin));
-        const float lse2 = m_fin + __builtin_amdgcn_logf(l_all);   // v_log_f32 = log2
+        // v_log_f32 = log2.  An utterance without a valid row (t_x <= 0): every logit is -inf and the sum is 0; a log-sum of
+        // 0 keeps its log-probs -inf (and soft 0) where -inf - -inf would be NaN
+        const float lse2 = (m_all == NEG_INF_F) ? 0.f : m_fin + __builtin_amdgcn_logf(l_all);
         SA_STAMP(4);
 
         // per-lane base + wave-uniform row offsets keep the addresses out of VGPRs; bounds tests
@@ -630,7 +632,7 @@ __global__ __launch_bounds__(SA_THREADS, (KS == 16 && MULTI) ? 1 : 2) void softa
 #pragma unroll
                     for (int e = 0; e < 16; ++e) s2 += __expf(lg[r][e] - m2m);
                 s2 += __shfl_xor(s2, 32);
-                lse2 = m2m + __logf(s2);
+                lse2 = (m2 == NEG_INF_F) ? 0.f : m2m + __logf(s2);       // (no valid row: soft 0, not NaN)
             }
 #pragma unroll
             for (int r = 0; r < G; ++r) {
@@ -692,7 +694,7 @@ __global__ __launch_bounds__(SA_THREADS, (KS == 16 && MULTI) ? 1 : 2) void softa
             const float m_fin = (m_all == NEG_INF_F) ? 0.f : m_all;
             const float l_all = (m_run == NEG_INF_F ? 0.f : l_run * __expf(m_run - m_fin)) +
                                 (m_o == NEG_INF_F ? 0.f : l_o * __expf(m_o - m_fin));
-            lse = m_fin + __logf(l_all);
+            lse = (m_all == NEG_INF_F) ? 0.f : m_fin + __logf(l_all);    // (no valid row: log-probs -inf, soft 0, not NaN)
         }
         for (int g = 0; g < NG; ++g) {
             const int row0 = 32 * G * g;
@@ -814,7 +816,8 @@ __device__ __forceinline__ float rt_merge(const float2 (&st)[NT]) {
     float L = 0.f;
 #pragma unroll
     for (int w = 0; w < NT; ++w) L = fmaf(st[w].y, __builtin_amdgcn_exp2f(st[w].x - Mf), L);
-    return -(Mf + __builtin_amdgcn_logf(L)) * LN2_F;           // v_log_f32 = log2
+    // v_log_f32 = log2; a frame of an utterance without a valid row (every maximum -inf): 0, so that its log-probs stay -inf
+    return (M == NEG_INF_F) ? 0.f : -(Mf + __builtin_amdgcn_logf(L)) * LN2_F;
 }
 
 // debug stamps: [workgroup][wave][64]: 0 entry, 1 operands staged, 2 first strip's MFMAs done, 5 end, 6 stores drained,
@@ -1237,10 +1240,11 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
 // --------------------------------------------------------------------------
 // Exact-product form of the same front end: the contraction on v_mfma_f32_32x32x2_f32 (fp32 operands, fp32
 // fma chain -- no operand splitting), a quarter of the bf16x3 kernel's matrix rate.  The bf16x3 product
-// (hi*hi + hi*lo + lo*hi, lo itself rounded to bf16) carries ~2^-16.5 relative error per product; the logit
-// multiplies the summed products by 2*temperature (L2) or temperature (dot), so the 1e-4 bound on logp holds
-// for the default temperature with a wide margin but not for sharp ones on large encodings (measured 5e-4 at
-// temperature 0.05, |k|,|q| ~ 3 per channel).  Host rule (aligner_softattn): L2 with temperature > 0.002, or
+// (hi*hi + hi*lo + lo*hi, lo itself rounded to bf16) carries up to 3 * 2^-16 relative error per product (2^-17 of the
+// summed magnitudes from 80 channels on: aligner_amd.h states the bound); the logit multiplies the summed products by
+// 2*temperature (L2) or temperature (dot), so 1e-4 on logp holds for the default temperature with a wide margin but not
+// for sharp ones on large encodings (measured 5e-4 at temperature 0.05, |k|,|q| ~ 3 per channel -- and, for dot, at
+// temperatures below its rule too: see the header).  Host rule (aligner_softattn): L2 with temperature > 0.002, or
 // dot with temperature > 0.2, takes this kernel; so does the "softattn_exact" debug option.
 // Plain structure (a correctness path): a workgroup = 4 waves = 128 frames of one utterance; text rows in
 // groups of GE 32-row tiles staged to LDS as fp32 A fragments; two sweeps over the groups (running max / sum,
@@ -1340,7 +1344,7 @@ __global__ __launch_bounds__(256) void softattn_exact_kernel(SoftAttnParams p, i
         const float m_fin = (m_all == NEG_INF_F) ? 0.f : m_all;
         const float l_all = (m_run == NEG_INF_F ? 0.f : l_run * __expf(m_run - m_fin)) +
                             (m_o == NEG_INF_F ? 0.f : l_o * __expf(m_o - m_fin));
-        lse = m_fin + __logf(l_all);
+        lse = (m_all == NEG_INF_F) ? 0.f : m_fin + __logf(l_all);        // (no valid row: log-probs -inf, soft 0, not NaN)
     }
     // with a prior the soft output needs a second normalisation: running max / sum of the final log-probs
     float m2 = NEG_INF_F, l2s = 0.f;
@@ -1351,8 +1355,8 @@ __global__ __launch_bounds__(256) void softattn_exact_kernel(SoftAttnParams p, i
             const float m_o = __shfl_xor(m2, 32), l_o = __shfl_xor(l2s, 32);
             const float m_all = fmaxf(m2, m_o);
             const float m_fin = (m_all == NEG_INF_F) ? 0.f : m_all;
-            lse2 = m_fin + __logf((m2 == NEG_INF_F ? 0.f : l2s * __expf(m2 - m_fin)) +
-                                  (m_o == NEG_INF_F ? 0.f : l_o * __expf(m_o - m_fin)));
+            lse2 = (m_all == NEG_INF_F) ? 0.f : m_fin + __logf((m2 == NEG_INF_F ? 0.f : l2s * __expf(m2 - m_fin)) +
+                                                               (m_o == NEG_INF_F ? 0.f : l_o * __expf(m_o - m_fin)));
         }
         for (int g = 0; g < NG; ++g) {
             __syncthreads();
@@ -1522,7 +1526,7 @@ int aligner_softattn_ld(const float *keys, const float *queries, const int32_t *
         if ((ld_logp * (logp_dtype == ALIGNER_DT_BF16 ? 2 : 4)) % 16 != 0)
             return fail(ALIGNER_EINVAL, "ld_logp=%d: rows must start on 16-byte boundaries", ld_logp);
     }
-    // sharp temperatures multiply the bf16x3 product error past the 1e-4 bound: exact fp32 products instead
+    // sharp temperatures multiply the bf16x3 product error past 1e-4 (L2; dot: see aligner_amd.h): exact fp32 products instead
     // (rule and reasoning: softattn_exact_kernel)
     const bool sharp = (sim == ALIGNER_SIM_L2) ? temperature > 0.002f : temperature > 0.2f;
     if (sharp || g_opt_softattn_exact) {

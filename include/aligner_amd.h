@@ -278,16 +278,29 @@ int aligner_maxpath_host_f32(int32_t *paths, float *values,
  * logp[b,i,j] = log_softmax_i( logit[b,i,j] ) (+ log(prior[b,i,j] + 1e-8))
  *   keys_dev    [B,C,Tx] fp32  encoded text  (channel-major, as Conv1d emits)
  *   queries_dev [B,C,Ty] fp32  encoded mel
- *   t_xs_dev    optional [B] int32: text rows >= t_x are excluded from the
- *               softmax and written as -inf; NULL = all Tx rows valid.
+ *   t_xs_dev    optional [B] int32 (clamped to [0, Tx]): text rows >= t_x are excluded from the
+ *               softmax and written as -inf (0 in soft_out_dev); NULL = all Tx rows valid.
  *   prior_dev   optional [B,Tx,Ty] fp32
  *   logp_out_dev [B,Tx,Ty] fp32; soft_out_dev optional [B,Tx,Ty] fp32 = softmax_i(logp)
  *   workspace_dev  aligner_softattn_workspace_bytes(B,C,Tx) bytes: the text operand split
  *               to bf16 halves in MFMA fragment order, prepared once per call.
  * Arithmetic: the contraction runs on the bf16 matrix cores with every fp32 operand split in two bf16 halves
- * (hi*hi + hi*lo + lo*hi, fp32 accumulate: ~2^-16 relative per product), which keeps |logp - fp32 reference|
- * below 1e-4 for temperature <= 0.002 (L2) / 0.2 (dot) on encodings of a few units per channel.  Sharper
- * temperatures take an exact-product kernel (fp32 MFMA, about a quarter of the matrix rate) automatically.
+ * (hi*hi + hi*lo + lo*hi, fp32 accumulate).  What that delivers, against the formula evaluated exactly on the fp32 inputs:
+ *     |logp[b,i,j] - exact| <= 2^-16 Scol[b,j] + 2^-23 |logp| + 6.5e-6      (C >= 80; 3 * 2^-15 Scol below)
+ *   Scol[b,j] = max over the rows i < t_x of S[b,i,j], the magnitude of what the logit adds up:
+ *     L2 : S = T (2 sum_c |k_ci| |q_cj| + sum_c k_ci^2 + sum_c q_cj^2)        dot: S = T sum_c |k_ci| |q_cj|
+ *   (an error in any row's logit moves the column's log-sum); 6.5e-6 is the log-sum-exp in fp32, whatever the logits.
+ * The absolute consequence, per similarity, at the sharpest temperature these kernels are given:
+ *   L2,  temperature <= 0.002: |logp - exact| < 1e-4 on encodings of a few units per channel (the error is multiplied
+ *        by 2T <= 0.004; C = 256 at 3 units per channel: about 1e-5);
+ *   dot, temperature <= 0.2:   |logp - exact| < 1e-4 on encodings of about ONE unit per channel only (the error is
+ *        multiplied by T: at 3 units per channel, or a common offset of 3, the three products alone are 7e-4 to 8e-4
+ *        off at T = 0.2 and 4e-4 at T = 0.11, C = 80 to 256); the bound above is what holds there.
+ * Sharper temperatures (L2 > 0.002, dot > 0.2) take an exact-product kernel (fp32 MFMA, about a quarter of the matrix
+ * rate) automatically: the same bound with 2^-16 replaced by 4 * 2^-24 e(C), e(C) = 9.5 at C = 80, 16 at C = 256 (an fp32
+ * sum over C channels).  tests/test_softattn_host.py derives every figure, tests/test_softattn_inputs_gpu.py holds the
+ * kernels to them.
+ * An utterance with t_x <= 0 (no valid row): logp is -inf and soft is 0 throughout, never NaN.
  */
 size_t aligner_softattn_workspace_bytes(int B, int C, int Tx);
 /* logp_out_dev of logp_dtype F32 or BF16 (round to nearest even; the layout aligner_maxpath reads directly:
