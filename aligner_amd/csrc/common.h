@@ -1,4 +1,5 @@
-// Shared host-side helpers for libaligner_amd.so (error reporting, HIP checks).
+// Shared helpers for libaligner_amd.so: host side (error reporting, HIP checks) and, at the end, the device-side
+// prefix sums of the durations that two kernel files share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -62,9 +63,53 @@ extern int g_opt_softattn_no_pair;     // "softattn_no_pair": testing, the simil
 extern int g_opt_mobo_bwd_general;     // "mobo_bwd_general": testing, the gradient's chain in its general (one exp2 per term) form
 extern int g_opt_mobo_lanes;           // "mobo_lanes": development, lanes per position in the split form (0: the plan's choice)
 extern int g_opt_mobo_drop_segment;    // "mobo_drop_segment": testing, that position segment never publishes (-1: off)
+extern int g_opt_gaussnll_rows;         // "gaussnll_rows": A-B / testing, rows per wave and pass of gauss_nll_kernel (1, 2, 4; never above what LDS allows at the T_text; 0: the launch's choice)
+extern int g_opt_gaussnll_grid;         // "gaussnll_grid": testing, at most this many workgroups per utterance in gauss_nll_kernel's launch, so that a workgroup takes several row groups (0: the launch's choice)
 extern int g_opt_fwdsum_no_grad_stager; // "fwdsum_no_grad_stager": A-B / testing, the gradient-making backward kernel with its compiler-scheduled stager
 extern int g_opt_fwdsum_serial;        // "fwdsum_serial": forward then backward sweep, never side by side (A/B, tests)
 extern int g_opt_fwdsum_one_wave;      // aligner_debug_set_option("fwdsum_one_wave", ...); default: env, read once
+
+// The durations' prefix sums and the owner lookup on them, shared by the kernels that work on the length regulator's
+// segments (hardalign.hip: segment_reduce_kernel, gaussnll.hip: gauss_nll_kernel).
+constexpr int DUR_SCAN_THREADS = 256;
+
+// ends[x] = sum(max(dur[b,i],0), i <= x) for one utterance, by the whole workgroup (256 threads): a thread sums
+// `per` consecutive tokens, the wave scans its 64 partial sums in registers, four wave totals go through LDS.
+__device__ inline void scan_durations(const int *__restrict__ dur_b, int *ends, int *wave_tot, int Tx) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (Tx + DUR_SCAN_THREADS - 1) / DUR_SCAN_THREADS;
+    const int x0 = tid * per;
+    int s = 0;
+    for (int i = 0; i < per; ++i) {
+        const int x = x0 + i;
+        int d = (x < Tx) ? dur_b[x] : 0;
+        d = d < 0 ? 0 : d;
+        s += d;
+        if (x < Tx) ends[x] = s;                             // local inclusive sum for now
+    }
+    int incl = s;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int base = incl - s;
+    for (int w = 0; w < wave; ++w) base += wave_tot[w];
+    for (int i = 0; i < per; ++i)
+        if (x0 + i < Tx) ends[x0 + i] += base;
+    __syncthreads();
+}
+
+// first x in [lo, Tx) with ends[x] > y; Tx when there is none (a frame past the durations' sum)
+__device__ inline int owner_of(const int *ends, int lo, int Tx, int y) {
+    int hi = Tx;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (ends[mid] > y) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -23,46 +23,8 @@
 
 namespace aligner {
 
-constexpr int SR_THREADS = 256;
+constexpr int SR_THREADS = DUR_SCAN_THREADS;    // (scan_durations, common.h)
 constexpr int SR_WAVES = SR_THREADS / 64;
-
-// ends[x] = sum(max(dur[b,i],0), i <= x) for one utterance, by the whole workgroup (256 threads): a thread sums
-// `per` consecutive tokens, the wave scans its 64 partial sums in registers, four wave totals go through LDS.
-__device__ inline void scan_durations(const int *__restrict__ dur_b, int *ends, int *wave_tot, int Tx) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (Tx + SR_THREADS - 1) / SR_THREADS;
-    const int x0 = tid * per;
-    int s = 0;
-    for (int i = 0; i < per; ++i) {
-        const int x = x0 + i;
-        int d = (x < Tx) ? dur_b[x] : 0;
-        d = d < 0 ? 0 : d;
-        s += d;
-        if (x < Tx) ends[x] = s;                             // local inclusive sum for now
-    }
-    int incl = s;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int base = incl - s;
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    for (int i = 0; i < per; ++i)
-        if (x0 + i < Tx) ends[x0 + i] += base;
-    __syncthreads();
-}
-
-// first x in [lo, Tx) with ends[x] > y; Tx when there is none (a frame past the durations' sum)
-__device__ inline int owner_of(const int *ends, int lo, int Tx, int y) {
-    int hi = Tx;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ends[mid] > y) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
 
 // VEC frames per lane (4: 16-byte loads, rows 16-byte aligned; 1: any Ty / pointer), CW rows per wave and pass.
 // LDS: ends[Tx] | wave_tot[4] | acc[SR_WAVES][CW][Tx] fp32.

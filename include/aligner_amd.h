@@ -42,7 +42,8 @@ extern "C" {
  *    aligner_conv1d_backward_weight_f32 / aligner_conv1d_backward_workspace_bytes; and the hard half of the training
  *    objective -- aligner_segment_reduce_f32, aligner_bin_loss, aligner_bin_loss_grad_f32; and the hard search with
  *    optional pauses between tokens -- aligner_pausepath / aligner_pausepath_workspace_bytes; and the Glow-TTS / VITS
- *    log-likelihood front end -- aligner_gauss_logp / aligner_gauss_logp_workspace_bytes. */
+ *    log-likelihood front end -- aligner_gauss_logp / aligner_gauss_logp_workspace_bytes; and their likelihood loss on
+ *    the hard path -- aligner_gauss_nll_f32 / aligner_gauss_nll_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -382,6 +383,42 @@ int aligner_gauss_logp(const float *z_dev, const float *mean_dev, const float *l
                        void *value_out_dev, int value_dtype, int ld_value,
                        void *workspace_dev, size_t workspace_bytes,
                        int B, int C, int Tx, int Ty, void *stream);
+
+/*
+ * The loss those models train on once the alignment is found: the negative log-likelihood of every latent frame under
+ * the Gaussian of the token that owns it, and its gradient.  With ends[x] = sum(max(durations[b,i],0), i <= x) -- the
+ * segments of aligner_regulate_f32 / aligner_segment_reduce_f32 -- token x owns the frames ends[x-1] <= y < ends[x]; a
+ * frame counts when it has an owner, y < Ty and, with t_ys_dev given, y < t_ys[b].  For a counting frame
+ * w = exp(-2 logstd[b,c,x]), d = z[b,c,y] - mean[b,c,x], and n_x is the number of counting frames of token x:
+ *   nll_out[b]        = sum over the counting frames and the channels of ( 1/2 ln 2pi + logstd[b,c,x] + 1/2 d^2 w )
+ *   count_out[b]      = number of counting frames (nll / (C count) is the Glow-TTS loss; a VITS KL term is nll minus
+ *                       quantities that do not depend on the alignment)
+ *   grad_z[b,c,y]     =  scale[b] d w                       (+0.0 on a frame that does not count)
+ *   grad_mean[b,c,x]  = -scale[b] sum_{y of x} d w          (+0.0 for a token without a counting frame)
+ *   grad_logstd[b,c,x] = scale[b] ( n_x - w sum_{y of x} d^2 )       (likewise)
+ *   z_dev [B,C,Ty], mean_dev and logstd_dev [B,C,Tx] fp32; durations_dev [B,Tx] int32; t_ys_dev optional [B] int32;
+ *   scale_dev optional [B] fp32 on the device, the upstream gradient of nll[b] (NULL: 1);
+ *   nll_out_dev optional [B] fp32; count_out_dev optional [B] int32;
+ *   grad_z_dev [B,C,Ty], grad_mean_dev and grad_logstd_dev [B,C,Tx] fp32: all three or none; every element is written;
+ *   workspace_dev  aligner_gauss_nll_workspace_bytes(B,C,Tx) bytes (0 for a shape that is not supported): one loss
+ *               partial per (utterance, channel) row.
+ * One streaming kernel reads z once (and writes grad_z once); a workgroup owns whole (utterance, channel) rows, the
+ * per-token sums are a segmented scan over the lanes into per-token accumulators in LDS; a second small kernel adds an
+ * utterance's C partials in a fixed order.  No atomics: the same bits on every call.  Ty % 4 == 0 with 16-byte aligned
+ * z_dev (and grad_z_dev) takes the 16-byte loads and stores.  fp32 throughout; a sum of n terms carries an error of at
+ * most (n + 8) 2^-24 times the sum of the terms' magnitudes.
+ * ALIGNER_EINVAL: a null z / mean / logstd / durations / workspace pointer, a shape below 1, one or two of the three
+ * gradient pointers, or no output at all.  ALIGNER_EDOM: Tx > 2048 (the segment reduction's limit), B > 65535, or
+ * B*C*max(Tx,Ty) past 2^31 - 1 (32-bit frame indexing).  ALIGNER_ENOSPC: workspace_bytes too small.  Arguments are
+ * validated before any HIP call.  One or two launches, asynchronous.
+ */
+size_t aligner_gauss_nll_workspace_bytes(int B, int C, int Tx);
+int aligner_gauss_nll_f32(const float *z_dev, const float *mean_dev, const float *logstd_dev,
+                          const int32_t *durations_dev, const int32_t *t_ys_dev, const float *scale_dev,
+                          float *nll_out_dev, int32_t *count_out_dev,
+                          float *grad_z_dev, float *grad_mean_dev, float *grad_logstd_dev,
+                          void *workspace_dev, size_t workspace_bytes,
+                          int B, int C, int Tx, int Ty, void *stream);
 
 /*
  * y[b,o,t] = act( bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2] ), zero padded
