@@ -1,5 +1,4 @@
-// Shared helpers for libaligner_amd.so: host side (error reporting, HIP checks) and, at the end, the device-side
-// prefix sums of the durations that two kernel files share.
+// Shared host-side helpers for libaligner_amd.so (error reporting, HIP checks, launch shapes) and the debug options.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -69,48 +68,23 @@ extern int g_opt_fwdsum_no_grad_stager; // "fwdsum_no_grad_stager": A-B / testin
 extern int g_opt_fwdsum_serial;        // "fwdsum_serial": forward then backward sweep, never side by side (A/B, tests)
 extern int g_opt_fwdsum_one_wave;      // aligner_debug_set_option("fwdsum_one_wave", ...); default: env, read once
 
-// The durations' prefix sums and the owner lookup on them, shared by the kernels that work on the length regulator's
-// segments (hardalign.hip: segment_reduce_kernel, gaussnll.hip: gauss_nll_kernel).
-constexpr int DUR_SCAN_THREADS = 256;
-
-// ends[x] = sum(max(dur[b,i],0), i <= x) for one utterance, by the whole workgroup (256 threads): a thread sums
-// `per` consecutive tokens, the wave scans its 64 partial sums in registers, four wave totals go through LDS.
-__device__ inline void scan_durations(const int *__restrict__ dur_b, int *ends, int *wave_tot, int Tx) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (Tx + DUR_SCAN_THREADS - 1) / DUR_SCAN_THREADS;
-    const int x0 = tid * per;
-    int s = 0;
-    for (int i = 0; i < per; ++i) {
-        const int x = x0 + i;
-        int d = (x < Tx) ? dur_b[x] : 0;
-        d = d < 0 ? 0 : d;
-        s += d;
-        if (x < Tx) ends[x] = s;                             // local inclusive sum for now
-    }
-    int incl = s;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int base = incl - s;
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    for (int i = 0; i < per; ++i)
-        if (x0 + i < Tx) ends[x0 + i] += base;
-    __syncthreads();
-}
-
-// first x in [lo, Tx) with ends[x] > y; Tx when there is none (a frame past the durations' sum)
-__device__ inline int owner_of(const int *ends, int lo, int Tx, int y) {
-    int hi = Tx;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ends[mid] > y) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Launch shape of the kernels in which a workgroup owns whole (utterance, channel) rows of the duration segments
+// (hardalign.hip: segment_reduce_kernel, gaussnll.hip: gauss_nll_kernel).
+// Workgroups per utterance for `ngroups` row groups: about SEGMENT_GRID_WORKGROUPS in all (256 CUs, eight resident each,
+// two rounds), a rule of thumb for streaming kernels, not a tuned value -- no other grid was timed.  Beyond it a
+// workgroup takes several row groups and pays the duration scan once for them.  cap > 0: at most that many.
+constexpr int SEGMENT_GRID_WORKGROUPS = 4096;
+inline int segment_grid_x(int B, int ngroups, int cap = 0) {
+    int gx = (SEGMENT_GRID_WORKGROUPS + B - 1) / B;
+    gx = gx < ngroups ? gx : ngroups;
+    return (cap > 0 && gx > cap) ? cap : gx;
+}
+
+// their dynamic LDS: ends[Tx] | wave_tot[waves] | acc[waves][rows][Tx] fp32, `rows` accumulator rows per wave
+inline size_t segment_lds_bytes(int Tx, int waves, int rows) {
+    return ((size_t)Tx + waves + (size_t)waves * rows * Tx) * sizeof(int);
+}
 
 }  // namespace aligner

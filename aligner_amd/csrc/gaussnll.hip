@@ -26,6 +26,7 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "segments.h"
 
 namespace aligner {
 
@@ -33,63 +34,6 @@ constexpr int GN_THREADS = DUR_SCAN_THREADS;
 constexpr int GN_WAVES = GN_THREADS / 64;
 typedef float __attribute__((ext_vector_type(4))) gn_f32x4;
 constexpr float GN_HALF_LN_2PI = 0.91893853320467274178f;
-
-// One row's share of a run: the lane's VEC values per quantity (v1 = d w, v2 = d^2) go into the row's two per-token
-// accumulators a1 / a2 in the order segment_reduce_kernel uses: the lane's head run | the runs wholly inside the lane
-// (flushed at once: nobody else holds their key) | its last run, joined with the lanes below by a segmented scan.
-template <int VEC>
-__device__ inline void gn_accumulate(const float (&v1)[VEC], const float (&v2)[VEC], const int (&k)[VEC], int Tx,
-                                     float *a1, float *a2, unsigned join, bool has_head, bool head_joins,
-                                     bool tail_ends) {
-    const int kt = k[VEC - 1];
-    float head1 = 0.f, head2 = 0.f, run1 = v1[0], run2 = v2[0];
-    if constexpr (VEC == 4) {
-        int rk = k[0];
-        bool head_done = false;
-#pragma unroll
-        for (int j = 1; j < 4; ++j) {
-            if (k[j] == rk) {
-                run1 += v1[j];
-                run2 += v2[j];
-            } else {
-                if (!head_done) {
-                    head1 = run1;
-                    head2 = run2;
-                    head_done = true;
-                } else if (rk < Tx) {
-                    a1[rk] += run1;
-                    a2[rk] += run2;
-                }
-                rk = k[j];
-                run1 = v1[j];
-                run2 = v2[j];
-            }
-        }
-    }
-    float s1 = run1, s2 = run2;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const float p1 = __shfl_up(s1, 1 << i);
-        const float p2 = __shfl_up(s2, 1 << i);
-        if (join & (1u << i)) {
-            s1 += p1;
-            s2 += p2;
-        }
-    }
-    const float below1 = __shfl_up(s1, 1);
-    const float below2 = __shfl_up(s2, 1);
-    __builtin_amdgcn_wave_barrier();
-    if (has_head && k[0] < Tx) {
-        a1[k[0]] += head_joins ? below1 + head1 : head1;
-        a2[k[0]] += head_joins ? below2 + head2 : head2;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (tail_ends && kt < Tx) {
-        a1[kt] += s1;
-        a2[kt] += s2;
-    }
-    __builtin_amdgcn_wave_barrier();
-}
 
 // VEC frames per lane (4: 16-byte loads and stores, rows 16-byte aligned; 1: any T_mel / pointer), CW rows per wave and
 // pass, GRAD: the gradients as well.  LDS: ends[Tx] | wave_tot[4] | GRAD only: acc[GN_WAVES][CW][2][Tx] fp32.
@@ -110,9 +54,7 @@ __global__ __launch_bounds__(GN_THREADS) void gauss_nll_kernel(const float *__re
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *acc = reinterpret_cast<float *>(wave_tot + GN_WAVES) + (size_t)wave * CW * 2 * Tx;
     scan_durations(dur + (size_t)b * Tx, ends, wave_tot, Tx);
-    int ty = t_ys ? t_ys[b] : Ty;
-    ty = ty < Ty ? ty : Ty;
-    ty = ty > 0 ? ty : 0;
+    const int ty = clamp_t_y(t_ys, b, Ty);
     float sc = 1.f;
     if constexpr (GRAD) {
         if (scale) sc = scale[b];
@@ -145,33 +87,10 @@ __global__ __launch_bounds__(GN_THREADS) void gauss_nll_kernel(const float *__re
                     zv[r][0] = *p;
                 }
             }
-            // keys of the lane's frames
-            int k[VEC];
-            k[0] = (y0 < ty) ? owner_of(ends, 0, Tx, y0) : Tx;
-            if constexpr (VEC == 4) {
-                k[3] = (y0 + 3 < ty) ? owner_of(ends, k[0], Tx, y0 + 3) : Tx;
-                if (k[3] == k[0]) {
-                    k[1] = k[2] = k[0];
-                } else {
-                    k[1] = (y0 + 1 < ty) ? owner_of(ends, k[0], Tx, y0 + 1) : Tx;
-                    k[2] = (y0 + 2 < ty) ? owner_of(ends, k[1], Tx, y0 + 2) : Tx;
-                }
-            }
-            const int kt = k[VEC - 1];
-            unsigned join = 0;                                // bit i: the lane 2^i below ends in the same key
-            bool has_head = false, head_joins = false, tail_ends = false;
-            if constexpr (GRAD) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const int pk = __shfl_up(kt, 1 << i);
-                    if (lane >= (1 << i) && pk == kt) join |= 1u << i;
-                }
-                const int k_prev = __shfl_up(kt, 1);          // (lane 0: its own, masked below)
-                const int k_next = __shfl_down(k[0], 1);
-                tail_ends = (lane == 63) || (k_next != kt);
-                has_head = (k[0] != kt);                      // a run that ends inside this lane's frames
-                head_joins = has_head && lane > 0 && k_prev == k[0];
-            }
+            int k[VEC];                                       // keys (segments.h), once per run for the CW rows
+            seg_keys<VEC>(ends, Tx, ty, y0, k);
+            SegJoin join = {};
+            if constexpr (GRAD) join = seg_join<VEC>(k, lane);
 #pragma unroll
             for (int r = 0; r < CW; ++r) {
                 const int cr = (c0 + r < C) ? r : 0;
@@ -205,14 +124,14 @@ __global__ __launch_bounds__(GN_THREADS) void gauss_nll_kernel(const float *__re
                         }
                     }
                 }
-                float v1[VEC], v2[VEC], o[VEC];
+                float v[2][VEC], o[VEC];                      // v: d w and d^2, what the tokens sum
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
                     const bool counts = k[j] < Tx;
                     const float d = zv[r][j] - mj[j];
                     const float dw = d * wj[j];
-                    v1[j] = counts ? dw : 0.f;
-                    v2[j] = counts ? d * d : 0.f;
+                    v[0][j] = counts ? dw : 0.f;
+                    v[1][j] = counts ? d * d : 0.f;
                     o[j] = counts ? sc * dw : 0.f;
                     q[r] += counts ? d * dw : 0.f;
                 }
@@ -226,8 +145,7 @@ __global__ __launch_bounds__(GN_THREADS) void gauss_nll_kernel(const float *__re
                             __builtin_nontemporal_store(o[0], p);
                         }
                     }
-                    float *a = acc + r * 2 * Tx;
-                    gn_accumulate<VEC>(v1, v2, k, Tx, a, a + Tx, join, has_head, head_joins, tail_ends);
+                    seg_accumulate<VEC, 2>(v, k, Tx, acc + r * 2 * Tx, Tx, join);
                 }
             }
         }
@@ -278,16 +196,10 @@ __global__ __launch_bounds__(64) void gauss_nll_finish_kernel(const float *__res
         n += __shfl_down(n, o);
     }
     if (lane == 0) {
-        int ty = t_ys ? t_ys[b] : Ty;
-        ty = ty < Ty ? ty : Ty;
-        ty = ty > 0 ? ty : 0;
+        const int ty = clamp_t_y(t_ys, b, Ty);
         if (nll) nll[b] = s;
         if (count) count[b] = n < ty ? (int)n : ty;
     }
-}
-
-static size_t gauss_nll_lds_bytes(int Tx, int cw, bool grad) {
-    return ((size_t)Tx + GN_WAVES + (grad ? (size_t)GN_WAVES * cw * 2 * Tx : 0)) * sizeof(int);
 }
 
 // Rows per wave and pass.  The two accumulator rows per channel row bound it (about 34 KiB of LDS at most up to
@@ -303,30 +215,33 @@ static int gauss_nll_rows_per_wave(int B, int C, int Tx) {
     return cw;
 }
 
+// one call's operands (scale, dz, dm, ds: null without the gradient)
+struct GaussNllArgs {
+    const float *z, *mean, *logstd;
+    const int32_t *dur, *t_ys;
+    const float *scale;
+    float *dz, *dm, *ds, *part;
+    int B, C, Tx, Ty;
+    hipStream_t stream;
+};
+
 template <int VEC, int CW, bool GRAD>
-static int launch_gauss_nll(const float *z, const float *mean, const float *logstd, const int32_t *dur,
-                            const int32_t *t_ys, const float *scale, float *dz, float *dm, float *ds, float *part,
-                            int B, int C, int Tx, int Ty, hipStream_t stream) {
-    const size_t lds = gauss_nll_lds_bytes(Tx, CW, GRAD);
+static int launch_gauss_nll(const GaussNllArgs &a) {
+    const size_t lds = segment_lds_bytes(a.Tx, GN_WAVES, GRAD ? 2 * CW : 0);
     ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(&gauss_nll_kernel<VEC, CW, GRAD>), lds));
-    const int ngroups = (C + GN_WAVES * CW - 1) / (GN_WAVES * CW);
-    int gx = (4096 + B - 1) / B;                              // (as launch_segment_reduce)
-    gx = gx < ngroups ? gx : ngroups;
-    if (g_opt_gaussnll_grid > 0 && gx > g_opt_gaussnll_grid) gx = g_opt_gaussnll_grid;
-    hipLaunchKernelGGL((gauss_nll_kernel<VEC, CW, GRAD>), dim3(gx, B), dim3(GN_THREADS), lds, stream, z, mean, logstd,
-                       dur, t_ys, scale, dz, dm, ds, part, C, Tx, Ty);
+    const int gx = segment_grid_x(a.B, (a.C + GN_WAVES * CW - 1) / (GN_WAVES * CW), g_opt_gaussnll_grid);
+    hipLaunchKernelGGL((gauss_nll_kernel<VEC, CW, GRAD>), dim3(gx, a.B), dim3(GN_THREADS), lds, a.stream, a.z, a.mean,
+                       a.logstd, a.dur, a.t_ys, a.scale, a.dz, a.dm, a.ds, a.part, a.C, a.Tx, a.Ty);
     ALIGNER_HIP_CHECK(hipGetLastError());
     return ALIGNER_OK;
 }
 
 template <int VEC, bool GRAD>
-static int launch_gauss_nll_cw(int cw, const float *z, const float *mean, const float *logstd, const int32_t *dur,
-                               const int32_t *t_ys, const float *scale, float *dz, float *dm, float *ds, float *part,
-                               int B, int C, int Tx, int Ty, hipStream_t stream) {
+static int launch_gauss_nll_cw(int cw, const GaussNllArgs &a) {
     switch (cw) {
-        case 4: return launch_gauss_nll<VEC, 4, GRAD>(z, mean, logstd, dur, t_ys, scale, dz, dm, ds, part, B, C, Tx, Ty, stream);
-        case 2: return launch_gauss_nll<VEC, 2, GRAD>(z, mean, logstd, dur, t_ys, scale, dz, dm, ds, part, B, C, Tx, Ty, stream);
-        default: return launch_gauss_nll<VEC, 1, GRAD>(z, mean, logstd, dur, t_ys, scale, dz, dm, ds, part, B, C, Tx, Ty, stream);
+        case 4: return launch_gauss_nll<VEC, 4, GRAD>(a);
+        case 2: return launch_gauss_nll<VEC, 2, GRAD>(a);
+        default: return launch_gauss_nll<VEC, 1, GRAD>(a);
     }
 }
 
@@ -366,13 +281,10 @@ int aligner_gauss_nll_f32(const float *z, const float *mean, const float *logstd
     const bool grad = ngrad == 3;
     const bool vec = (Ty % 4 == 0) && (reinterpret_cast<uintptr_t>(z) % 16 == 0) &&
                      (!grad || reinterpret_cast<uintptr_t>(grad_z) % 16 == 0);
-    int rc;
-    if (grad)
-        rc = vec ? launch_gauss_nll_cw<4, true>(cw, z, mean, logstd, durations, t_ys, scale, grad_z, grad_mean, grad_logstd, part, B, C, Tx, Ty, s)
-                 : launch_gauss_nll_cw<1, true>(cw, z, mean, logstd, durations, t_ys, scale, grad_z, grad_mean, grad_logstd, part, B, C, Tx, Ty, s);
-    else
-        rc = vec ? launch_gauss_nll_cw<4, false>(cw, z, mean, logstd, durations, t_ys, nullptr, nullptr, nullptr, nullptr, part, B, C, Tx, Ty, s)
-                 : launch_gauss_nll_cw<1, false>(cw, z, mean, logstd, durations, t_ys, nullptr, nullptr, nullptr, nullptr, part, B, C, Tx, Ty, s);
+    const GaussNllArgs a = {z, mean, logstd, durations, t_ys, grad ? scale : nullptr, grad_z, grad_mean, grad_logstd, part,
+                            B, C, Tx, Ty, s};
+    const int rc = grad ? (vec ? launch_gauss_nll_cw<4, true>(cw, a) : launch_gauss_nll_cw<1, true>(cw, a))
+                        : (vec ? launch_gauss_nll_cw<4, false>(cw, a) : launch_gauss_nll_cw<1, false>(cw, a));
     if (rc != ALIGNER_OK) return rc;
     if (nll_out || count_out) {
         hipLaunchKernelGGL(gauss_nll_finish_kernel, dim3(B), dim3(64), 0, s, part, durations, t_ys, nll_out, count_out,

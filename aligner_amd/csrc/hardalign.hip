@@ -20,17 +20,16 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "segments.h"
 
 namespace aligner {
 
-constexpr int SR_THREADS = DUR_SCAN_THREADS;    // (scan_durations, common.h)
+constexpr int SR_THREADS = DUR_SCAN_THREADS;    // (scan_durations, segments.h)
 constexpr int SR_WAVES = SR_THREADS / 64;
 
 // VEC frames per lane (4: 16-byte loads, rows 16-byte aligned; 1: any Ty / pointer), CW rows per wave and pass.
 // LDS: ends[Tx] | wave_tot[4] | acc[SR_WAVES][CW][Tx] fp32.
-// The key of a frame is its token, Tx for a frame no token owns (past the sum, or past Ty): keys never decrease
-// along a row, so "same key as the lane o below" is all a segmented scan needs.  Keys are per run of frames, not
-// per row: they and the scan's join masks are made once and used for the CW rows.
+// Keys, joins and the accumulation into acc: segments.h.
 template <int VEC, int CW>
 __global__ __launch_bounds__(SR_THREADS) void segment_reduce_kernel(const float *__restrict__ frames,
                                                                     const int *__restrict__ dur,
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(SR_THREADS) void segment_reduce_kernel(const float 
         for (int base = 0; base < Ty; base += 64 * VEC) {
             const int y0 = base + lane * VEC;
             // the loads first (addresses clamped into the row: what a frame without an owner holds is never used)
-            float v[CW][VEC];
+            float v[CW][1][VEC];                              // (one quantity per frame)
             {
                 const int yl = (y0 + VEC <= Ty) ? y0 : 0;
 #pragma unroll
@@ -65,70 +64,17 @@ __global__ __launch_bounds__(SR_THREADS) void segment_reduce_kernel(const float 
                     const float *p = row0 + (size_t)(c - c0) * Ty + yl;
                     if constexpr (VEC == 4) {
                         const float4 q = *reinterpret_cast<const float4 *>(p);
-                        v[r][0] = q.x; v[r][1] = q.y; v[r][2] = q.z; v[r][3] = q.w;
+                        v[r][0][0] = q.x; v[r][0][1] = q.y; v[r][0][2] = q.z; v[r][0][3] = q.w;
                     } else {
-                        v[r][0] = *p;
+                        v[r][0][0] = *p;
                     }
                 }
             }
-            // keys of the lane's frames
-            int k[VEC];
-            k[0] = (y0 < Ty) ? owner_of(ends, 0, Tx, y0) : Tx;
-            if constexpr (VEC == 4) {
-                k[3] = (y0 + 3 < Ty) ? owner_of(ends, k[0], Tx, y0 + 3) : Tx;
-                if (k[3] == k[0]) {
-                    k[1] = k[2] = k[0];
-                } else {
-                    k[1] = (y0 + 1 < Ty) ? owner_of(ends, k[0], Tx, y0 + 1) : Tx;
-                    k[2] = (y0 + 2 < Ty) ? owner_of(ends, k[1], Tx, y0 + 2) : Tx;
-                }
-            }
-            const int kt = k[VEC - 1];                        // key of the lane's last run
-            unsigned join = 0;                                // bit i: the lane 2^i below ends in the same key
+            int k[VEC];                                       // keys, joins: once per run, for the CW rows
+            seg_keys<VEC>(ends, Tx, Ty, y0, k);
+            const SegJoin join = seg_join<VEC>(k, lane);
 #pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const int pk = __shfl_up(kt, 1 << i);
-                if (lane >= (1 << i) && pk == kt) join |= 1u << i;
-            }
-            const int k_prev = __shfl_up(kt, 1);              // (lane 0: its own, masked below)
-            const int k_next = __shfl_down(k[0], 1);
-            const bool tail_ends = (lane == 63) || (k_next != kt);
-            const bool has_head = (k[0] != kt);               // a run that ends inside this lane's frames
-            const bool head_joins = has_head && lane > 0 && k_prev == k[0];
-#pragma unroll
-            for (int r = 0; r < CW; ++r) {
-                float *a = acc + r * Tx;
-                // the lane's own frames, in order: head run | runs wholly inside (flushed at once) | last run
-                float head = 0.f, run = v[r][0];
-                if constexpr (VEC == 4) {
-                    int rk = k[0];
-                    bool head_done = false;
-#pragma unroll
-                    for (int j = 1; j < 4; ++j) {
-                        if (k[j] == rk) {
-                            run += v[r][j];
-                        } else {
-                            if (!head_done) { head = run; head_done = true; }
-                            else if (rk < Tx) a[rk] += run;   // (a run between two others: nobody else has its key)
-                            rk = k[j];
-                            run = v[r][j];
-                        }
-                    }
-                }
-                // segmented inclusive scan of the last runs over the lanes
-                float s = run;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const float pv = __shfl_up(s, 1 << i);
-                    if (join & (1u << i)) s += pv;
-                }
-                const float below = __shfl_up(s, 1);
-                __builtin_amdgcn_wave_barrier();
-                if (has_head && k[0] < Tx) a[k[0]] += head_joins ? below + head : head;
-                __builtin_amdgcn_wave_barrier();
-                if (tail_ends && kt < Tx) a[kt] += s;
-                __builtin_amdgcn_wave_barrier();
-            }
+            for (int r = 0; r < CW; ++r) seg_accumulate<VEC, 1>(v[r], k, Tx, acc + r * Tx, 0, join);
         }
         // write the rows out along x and clear the accumulators for the next pass
         for (int r = 0; r < CW && c0 + r < C; ++r) {
@@ -177,8 +123,7 @@ __global__ __launch_bounds__(256) void bin_loss_kernel(const void *__restrict__ 
     __shared__ float wsum[4];
     __shared__ int wcnt[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    int ty = t_ys ? t_ys[b] : Ty;
-    ty = ty < Ty ? ty : Ty;
+    const int ty = clamp_t_y(t_ys, b, Ty);
     float s = 0.f;
     int n = 0;
     for (int y = tid; y < Ty; y += 256) {
@@ -209,8 +154,7 @@ __global__ __launch_bounds__(256) void bin_grad_scatter_kernel(const void *__res
                                                                float *__restrict__ grad, int Tx, int Ty) {
     const int b = blockIdx.y, y = blockIdx.x * 256 + threadIdx.x;
     if (y >= Ty) return;
-    int ty = t_ys ? t_ys[b] : Ty;
-    ty = ty < Ty ? ty : Ty;
+    const int ty = clamp_t_y(t_ys, b, Ty);
     int x;
     float lp;
     if (path_cell(logp, dtype, ld, tok, b, y, Tx, Ty, ty, &x, &lp) && lp > min_logp)
@@ -229,8 +173,7 @@ __global__ __launch_bounds__(256) void bin_grad_write_kernel(const void *__restr
     if (y0 >= Ty) return;
     const int xpz = (Tx + gridDim.z - 1) / gridDim.z;
     const int x0 = blockIdx.z * xpz, x1 = (x0 + xpz < Tx) ? x0 + xpz : Tx;
-    int ty = t_ys ? t_ys[b] : Ty;
-    ty = ty < Ty ? ty : Ty;
+    const int ty = clamp_t_y(t_ys, b, Ty);
     const float g = -scale[b];
     int hot[VEC];                                             // the row that gets g in this column, -1: none here
 #pragma unroll
@@ -265,13 +208,8 @@ static int segment_reduce_rows_per_wave(int Tx) { return Tx <= 512 ? 4 : (Tx <= 
 template <int VEC, int CW>
 static int launch_segment_reduce(const float *frames, const int32_t *dur, float *tokens, int B, int C, int Tx, int Ty,
                                  int mean, hipStream_t stream) {
-    const size_t lds = ((size_t)Tx + SR_WAVES + (size_t)SR_WAVES * CW * Tx) * sizeof(int);
-    const int ngroups = (C + SR_WAVES * CW - 1) / (SR_WAVES * CW);
-    // ~4096 workgroups (256 CUs, eight resident each, two rounds): a rule of thumb for streaming kernels, not a
-    // tuned value -- no other grid was timed.  Beyond it a workgroup takes several row groups and pays the
-    // duration scan once for them.
-    int gx = (4096 + B - 1) / B;
-    gx = gx < ngroups ? gx : ngroups;
+    const size_t lds = segment_lds_bytes(Tx, SR_WAVES, CW);
+    const int gx = segment_grid_x(B, (C + SR_WAVES * CW - 1) / (SR_WAVES * CW));
     hipLaunchKernelGGL((segment_reduce_kernel<VEC, CW>), dim3(gx, B), dim3(SR_THREADS), lds, stream, frames, dur,
                        tokens, C, Tx, Ty, mean);
     ALIGNER_HIP_CHECK(hipGetLastError());

@@ -17,6 +17,7 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "segments.h"
 
 namespace aligner {
 
@@ -67,49 +68,19 @@ __global__ __launch_bounds__(256) void prior_kernel(const int *__restrict__ t_xs
     for (int x = n; x < Tx; ++x) out[(size_t)x * Ty] = 0.f;
 }
 
-// durations -> token of every frame (inclusive scan in LDS, bisection per frame) -> gather.
+// durations -> token of every frame (scan_durations, owner_of: segments.h) -> gather.
 // One workgroup per 256 frames of one utterance; the scan of <= 2048 durations is redone per workgroup.
+static_assert(DUR_SCAN_THREADS == 256, "regulate_kernel: a thread per frame of the workgroup's 256, all of them in the scan");
 __global__ __launch_bounds__(256) void regulate_kernel(const float *__restrict__ h, const int *__restrict__ dur,
                                                        float *__restrict__ out, int *__restrict__ tok_out, int C,
                                                        int Tx, int Ty) {
-    extern __shared__ int ends[];                            // ends[x] = sum(dur[0..x]); ends[Tx..] scratch
-    int *part = ends + Tx;                                   // [256] per-thread partial sums
+    extern __shared__ int ends[];                            // ends[x] = sum(dur[0..x]) | the scan's wave totals
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int per = (Tx + 255) / 256;                        // consecutive tokens per thread
-    const int x0 = tid * per;
-    int s = 0;
-    for (int i = 0; i < per; ++i) {
-        const int x = x0 + i;
-        int d = (x < Tx) ? dur[(size_t)b * Tx + x] : 0;
-        d = d < 0 ? 0 : d;
-        s += d;
-        if (x < Tx) ends[x] = s;                             // local inclusive sum for now
-    }
-    part[tid] = s;
-    __syncthreads();
-    // exclusive scan of the 256 partials (Hillis-Steele in place, 8 rounds)
-    for (int o = 1; o < 256; o <<= 1) {
-        const int v = (tid >= o) ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    const int base = (tid > 0) ? part[tid - 1] : 0;
-    for (int i = 0; i < per; ++i)
-        if (x0 + i < Tx) ends[x0 + i] += base;
-    __syncthreads();
+    scan_durations(dur + (size_t)b * Tx, ends, ends + Tx, Tx);
     const int y = blockIdx.x * 256 + tid;
     if (y >= Ty) return;
-    const int total = ends[Tx - 1];
-    int tok = -1;
-    if (y < total) {                                         // first x with ends[x] > y
-        int lo = 0, hi = Tx - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ends[mid] > y) hi = mid; else lo = mid + 1;
-        }
-        tok = lo;
-    }
+    const int x = owner_of(ends, 0, Tx, y);
+    const int tok = x < Tx ? x : -1;                         // (a frame past the durations' sum)
     if (tok_out && blockIdx.z == 0) tok_out[(size_t)b * Ty + y] = tok;
     if (out) {
         // this workgroup's slice of the channels (gridDim.z slices), eight gathers in flight per thread.
@@ -177,7 +148,7 @@ int aligner_regulate_f32(const float *h, const int32_t *durations, float *out, i
         while (nz < 16 && wgs * nz < 2048 && C / (nz * 2) >= 16) nz *= 2;
     }
     dim3 grid((Ty + 255) / 256, B, nz);
-    hipLaunchKernelGGL(regulate_kernel, grid, dim3(256), (size_t)(Tx + 256) * sizeof(int),
+    hipLaunchKernelGGL(regulate_kernel, grid, dim3(256), (size_t)(Tx + DUR_SCAN_THREADS / 64) * sizeof(int),
                        static_cast<hipStream_t>(stream), h, durations, out, tok_out, C, Tx, Ty);
     ALIGNER_HIP_CHECK(hipGetLastError());
     return ALIGNER_OK;

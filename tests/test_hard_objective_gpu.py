@@ -105,8 +105,11 @@ def _durations(kind, B, Tx, Ty, rng, dev):
     return dur.astype(np.int32)
 
 
+# The last four: three row groups (the last with rows past C) on the two workgroups an utterance gets at B = 2100, so a
+# workgroup takes a second group, with one and with four frames per lane; and two rows per wave (512 < T_text <= 1024),
+# four and one frames per lane, again with a row past C.
 SEG_SHAPES = [(3, 5, 7, 19), (4, 80, 64, 200), (2, 512, 200, 1000), (2, 33, 300, 1023), (1, 16, 2048, 4000),
-              (64, 512, 200, 1000)]
+              (64, 512, 200, 1000), (2100, 33, 5, 19), (2100, 33, 7, 20), (2, 9, 600, 1200), (1, 9, 600, 1201)]
 SEG_KINDS = ["align", "skewed", "zeros_neg", "over", "under"]
 
 
@@ -129,19 +132,20 @@ def test_segment_reduce(dev, shape, kind):
 
 
 def test_the_restated_segments_are_the_regulator_s(dev):
-    """The segments of the float64 restatement are the ones regulate() expands over (its tok output)."""
+    """The segments of the float64 restatement are the ones regulate() expands over (its tok output); the second shape
+    has three tokens per thread in the durations' scan."""
     import aligner_amd
     rng = np.random.default_rng(5)
-    B, C, Tx, Ty = 3, 6, 50, 333
-    dur = _durations("zeros_neg", B, Tx, Ty, rng, dev)
-    dd = torch.from_numpy(dur).to(dev)
-    _, tok = aligner_amd.regulate(torch.zeros(B, C, Tx, device=dev), dd, Ty)
-    s, e = _segments(dur, Ty)
-    want = np.full((B, Ty), -1, np.int32)
-    for b in range(B):
-        for x in range(Tx):
-            want[b, s[b, x]:e[b, x]] = x
-    assert np.array_equal(tok.cpu().numpy(), want)
+    for B, C, Tx, Ty in [(3, 6, 50, 333), (2, 3, 700, 1500)]:
+        dur = _durations("zeros_neg", B, Tx, Ty, rng, dev)
+        dd = torch.from_numpy(dur).to(dev)
+        _, tok = aligner_amd.regulate(torch.zeros(B, C, Tx, device=dev), dd, Ty)
+        s, e = _segments(dur, Ty)
+        want = np.full((B, Ty), -1, np.int32)
+        for b in range(B):
+            for x in range(Tx):
+                want[b, s[b, x]:e[b, x]] = x
+        assert np.array_equal(tok.cpu().numpy(), want), (B, C, Tx, Ty)
 
 
 # ---------------------------------------------------------------- regulate / average_by_duration autograd
