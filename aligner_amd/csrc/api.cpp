@@ -27,6 +27,7 @@ int g_opt_fwdsum_serial = env_flag("ALIGNER_FWDSUM_SERIAL");
 int g_opt_fwdsum_no_grad_stager = 0;
 int g_opt_gaussnll_rows = 0;
 int g_opt_gaussnll_grid = 0;
+int g_opt_gaussup_full_range = 0;
 int g_opt_softattn_exact = env_flag("ALIGNER_SOFTATTN_EXACT");
 int g_opt_mobo_drop_segment = -1;
 int g_opt_mobo_start_lag = 0;
@@ -122,6 +123,7 @@ int aligner_debug_set_option(const char *name, int value) {
     if (std::strcmp(name, "fwdsum_no_grad_stager") == 0) { aligner::g_opt_fwdsum_no_grad_stager = value; return ALIGNER_OK; }
     if (std::strcmp(name, "gaussnll_rows") == 0) { aligner::g_opt_gaussnll_rows = value; return ALIGNER_OK; }
     if (std::strcmp(name, "gaussnll_grid") == 0) { aligner::g_opt_gaussnll_grid = value; return ALIGNER_OK; }
+    if (std::strcmp(name, "gaussup_full_range") == 0) { aligner::g_opt_gaussup_full_range = value; return ALIGNER_OK; }
     if (std::strcmp(name, "fwdsum_serial") == 0) { aligner::g_opt_fwdsum_serial = value; return ALIGNER_OK; }
     if (std::strcmp(name, "softattn_exact") == 0) { aligner::g_opt_softattn_exact = value; return ALIGNER_OK; }
     if (std::strcmp(name, "mobo_start_lag") == 0) { aligner::g_opt_mobo_start_lag = value; return ALIGNER_OK; }

@@ -64,6 +64,7 @@ extern int g_opt_mobo_lanes;           // "mobo_lanes": development, lanes per p
 extern int g_opt_mobo_drop_segment;    // "mobo_drop_segment": testing, that position segment never publishes (-1: off)
 extern int g_opt_gaussnll_rows;         // "gaussnll_rows": A-B / testing, rows per wave and pass of gauss_nll_kernel (1, 2, 4; never above what LDS allows at the T_text; 0: the launch's choice)
 extern int g_opt_gaussnll_grid;         // "gaussnll_grid": testing, at most this many workgroups per utterance in gauss_nll_kernel's launch, so that a workgroup takes several row groups (0: the launch's choice)
+extern int g_opt_gaussup_full_range;    // "gaussup_full_range": A-B / testing, every frame tile of the Gaussian upsampling kernels takes the full token range [0, t_x) (the path of centres that are out of order)
 extern int g_opt_fwdsum_no_grad_stager; // "fwdsum_no_grad_stager": A-B / testing, the gradient-making backward kernel with its compiler-scheduled stager
 extern int g_opt_fwdsum_serial;        // "fwdsum_serial": forward then backward sweep, never side by side (A/B, tests)
 extern int g_opt_fwdsum_one_wave;      // aligner_debug_set_option("fwdsum_one_wave", ...); default: env, read once

@@ -43,7 +43,8 @@ extern "C" {
  *    objective -- aligner_segment_reduce_f32, aligner_bin_loss, aligner_bin_loss_grad_f32; and the hard search with
  *    optional pauses between tokens -- aligner_pausepath / aligner_pausepath_workspace_bytes; and the Glow-TTS / VITS
  *    log-likelihood front end -- aligner_gauss_logp / aligner_gauss_logp_workspace_bytes; and their likelihood loss on
- *    the hard path -- aligner_gauss_nll_f32 / aligner_gauss_nll_workspace_bytes. */
+ *    the hard path -- aligner_gauss_nll_f32 / aligner_gauss_nll_workspace_bytes; and Gaussian upsampling with its
+ *    gradient -- aligner_gauss_upsample_f32 / aligner_gauss_upsample_backward_f32 and their *_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -419,6 +420,52 @@ int aligner_gauss_nll_f32(const float *z_dev, const float *mean_dev, const float
                           float *grad_z_dev, float *grad_mean_dev, float *grad_logstd_dev,
                           void *workspace_dev, size_t workspace_bytes,
                           int B, int C, int Tx, int Ty, void *stream);
+
+/*
+ * Gaussian upsampling, the differentiable length regulator of JETS, Non-Attentive Tacotron, Parallel Tacotron and
+ * ESPnet's GaussianUpsampling.  Frame y sits at tau_y = y + frame_offset; with tx = clamp(t_xs[b], 0, Tx) and
+ * ty = clamp(t_ys[b], 0, Ty) (NULL: the full extent),
+ *   e[b,y,x]   = log_weight[b,x] - precision[b,x] (tau_y - centre[b,x])^2        x < tx
+ *   p[b,y,.]   = softmax over those x
+ *   out[b,:,y] = sum_x p[b,y,x] h[b,:,x]                                          y < ty; +0.0 beyond, and everywhere
+ *                                                                                 when tx = 0
+ * and backward, with G = g_out (a frame y >= ty contributes nothing, whatever g_out holds there),
+ *   q[y,x] = sum_c G[c,y] h[c,x]     r[y] = sum_x p q     de[y,x] = p (q - r)
+ *   dh[c,x] = sum_y p[y,x] G[c,y]    dlog_weight[x] = sum_y de    dprecision[x] = -sum_y de (tau_y - centre_x)^2
+ *   dcentre[x] = sum_y de 2 precision_x (tau_y - centre_x)
+ *   h_dev [B,C,Tx], out_dev / g_out_dev [B,C,Ty] fp32; centre_dev, precision_dev [B,Tx] fp32 (precision >= 0: a negative
+ *   one is the caller's error and is not checked); log_weight_dev optional [B,Tx] fp32 (NULL: 0); t_xs_dev, t_ys_dev
+ *   optional [B] int32; dh_dev [B,C,Tx], dcentre_dev / dprecision_dev / dlog_weight_dev [B,Tx]: each may be NULL (not
+ *   wanted; at least one is), every element of a given one is written, +0.0 for a token x >= tx and everywhere for an
+ *   utterance with tx = 0 or ty = 0.
+ * Truncation is part of the contract: a kernel may treat as zero any token whose energy is more than
+ * ALIGNER_GAUSS_UP_CUT below the frame's largest energy, and includes every other token (e^-30 = 9.4e-14: nothing against
+ * 2^-24 for Tx <= 2048).  With the centres non-decreasing over x < tx a tile of 64 frames then needs one contiguous token
+ * interval, found from the centres, the utterance's smallest precision and largest log-weight; an utterance whose centres
+ * are out of order, or whose precision is not positive everywhere, or that holds a value that is not finite, takes the
+ * full token range: slower, the same definition.  The weights are never stored; the backward pass recomputes them and
+ * does not need out.  fp32 arithmetic, exact products (no matrix cores), the denominator summed in double; no
+ * floating-point atomics: the same bits on every call.  Forward: two launches; backward: three or four.
+ *   workspace_dev  aligner_gauss_upsample_workspace_bytes / aligner_gauss_upsample_backward_workspace_bytes (B,C,Tx,Ty)
+ *               bytes (0 for a shape that is not supported): the tiles' token intervals; backward also the frames'
+ *               maxima and denominators and six partial sums per (frame tile, token).
+ * ALIGNER_EINVAL: a null required pointer, a shape below 1, no output requested.  ALIGNER_EDOM: Tx > 2048 (the duration
+ * kernels' limit), B > 65535.  ALIGNER_ENOSPC: workspace_bytes too small.  Arguments are validated before any HIP call.
+ */
+#define ALIGNER_GAUSS_UP_CUT 30.0f
+size_t aligner_gauss_upsample_workspace_bytes(int B, int C, int Tx, int Ty);
+int aligner_gauss_upsample_f32(const float *h_dev, const float *centre_dev, const float *precision_dev,
+                               const float *log_weight_dev, const int32_t *t_xs_dev, const int32_t *t_ys_dev,
+                               float frame_offset, float *out_dev,
+                               void *workspace_dev, size_t workspace_bytes,
+                               int B, int C, int Tx, int Ty, void *stream);
+size_t aligner_gauss_upsample_backward_workspace_bytes(int B, int C, int Tx, int Ty);
+int aligner_gauss_upsample_backward_f32(const float *h_dev, const float *centre_dev, const float *precision_dev,
+                                        const float *log_weight_dev, const int32_t *t_xs_dev, const int32_t *t_ys_dev,
+                                        float frame_offset, const float *g_out_dev,
+                                        float *dh_dev, float *dcentre_dev, float *dprecision_dev, float *dlog_weight_dev,
+                                        void *workspace_dev, size_t workspace_bytes,
+                                        int B, int C, int Tx, int Ty, void *stream);
 
 /*
  * y[b,o,t] = act( bias[o] + sum_{i,k} w[o,i,k] * x[b,i,t+k-K/2] ), zero padded
