@@ -106,6 +106,8 @@ SIGNATURES = {
     "aligner_pausepath": (_i, [_vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "aligner_gauss_logp_workspace_bytes": (_sz, [_i, _i, _i]),
     "aligner_gauss_logp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "aligner_gauss_logp_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aligner_gauss_logp_backward_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "aligner_gauss_nll_workspace_bytes": (_sz, [_i, _i, _i]),
     "aligner_gauss_nll_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "aligner_gauss_upsample_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -7,6 +7,11 @@ Both models search the alignment on the log-density of every latent frame under 
 with m, s [B,C,T_text] the text encoder's mean and log-std and z [B,C,T_mel] the flow's output, computed under no_grad
 (the loss goes through the expanded m and s: regulate()).  gaussian_logp() is that tensor in one fused kernel;
 gaussian_align() is the whole `logp = ...; attn = maximum_path(logp, mask)` block of a training step.
+
+Models that train the tensor softly (AlignTTS's mixture-density loss, soft-alignment variants of Glow-TTS / VITS) need
+its gradient: gaussian_logp_backward() is the vector-Jacobian product (csrc/gausslogp_bwd.hip),
+gaussian_logp(differentiable=True) attaches it to autograd, and gaussian_forward_sum_loss() is the marginal likelihood
+over all monotonic alignments of the Gaussian scores as one autograd function.
 """
 from __future__ import annotations
 
@@ -16,6 +21,7 @@ import torch
 
 from . import _lib
 from .maxpath import Alignment, align
+from .objective import forward_sum
 from .softattn import pitched_logp
 
 _workspaces = _lib.StreamWorkspaces(zero=False)
@@ -30,7 +36,8 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 
 def gaussian_logp(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_x: Optional[torch.Tensor] = None,
                   t_y: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
-                  out_dtype: torch.dtype = torch.float32, pitched: bool = False) -> torch.Tensor:
+                  out_dtype: torch.dtype = torch.float32, pitched: bool = False,
+                  differentiable: bool = False) -> torch.Tensor:
     """value[b,i,j] = log N(z[b,:,j]; mean[b,:,i], exp(logstd[b,:,i])^2), [B,T_text,T_mel].
 
     z [B,C,T_mel], mean and logstd [B,C,T_text]: GPU tensors, channel-major as both models hold them (other dtypes than
@@ -39,7 +46,17 @@ def gaussian_logp(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_x
     the traffic; align() / maximum_path() read it as it is).  pitched: return a [B,T_text,T_mel] VIEW of a buffer whose
     rows start on whole 128-byte lines (pitched_logp(): what align() reads fastest).  out: write into the caller's
     tensor, contiguous or such a view (its dtype decides); the columns >= T_mel of a pitched buffer are never touched.
-    No gradient: the result never requires grad.  Asynchronous on the current stream."""
+    No gradient by default: the result never requires grad.  differentiable=True: when z, mean or logstd requires grad
+    the result is attached to autograd (the same forward kernel; the three inputs are saved, not the value; backward is
+    gaussian_logp_backward() for the inputs that need it, gradients in each input's dtype); out_dtype must then be fp32
+    and `out` is refused.  Asynchronous on the current stream."""
+    if differentiable:
+        if out is not None:
+            raise ValueError("differentiable=True cannot write into `out`")
+        if out_dtype != torch.float32:
+            raise ValueError("differentiable=True needs out_dtype torch.float32")
+        if any(isinstance(t, torch.Tensor) and t.requires_grad for t in (z, mean, logstd)) and torch.is_grad_enabled():
+            return _GaussianLogp.apply(z, mean, logstd, t_x, t_y, pitched)
     for t, name in ((z, "z"), (mean, "mean"), (logstd, "logstd")):
         if not isinstance(t, torch.Tensor) or t.dim() != 3:
             raise ValueError(f"{name} must be a [B,C,T] tensor")
@@ -107,3 +124,155 @@ def gaussian_align(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_
         raise ValueError("gaussian_align needs the lengths t_x and t_y")
     logp = gaussian_logp(z, mean, logstd, t_x, t_y, out_dtype=logp_dtype, pitched=True)
     return align(logp, t_x, t_y, **align_kwargs)
+
+
+def _grad_layout(g: torch.Tensor, B: int, Tx: int, Ty: int):
+    """grad_value as the kernel reads it: (fp32 tensor, row pitch).  Contiguous, or pitched_logp()'s view, is read in
+    place; anything else is copied."""
+    g = g.detach()
+    if g.dtype == torch.float32 and g.stride(2) == 1 and Ty > 1 and Tx > 1:
+        ld = int(g.stride(1))
+        if ld >= Ty and (B == 1 or g.stride(0) == Tx * ld) and (ld == Ty or (ld * 4) % 16 == 0):
+            return g, ld
+    return g.float().contiguous(), Ty
+
+
+def gaussian_logp_backward(grad_value: torch.Tensor, z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor,
+                           t_x: Optional[torch.Tensor] = None, t_y: Optional[torch.Tensor] = None, *,
+                           grad_scale: Optional[torch.Tensor] = None, need_z: bool = True, need_mean: bool = True,
+                           need_logstd: bool = True):
+    """The vector-Jacobian product of gaussian_logp(): (dz [B,C,T_mel], dmean, dlogstd [B,C,T_text]) for the cotangent
+    grad_value [B,T_text,T_mel] (fp32; contiguous or at pitched_logp()'s row pitch, read in place), fp32, None where
+    need_* is False.  t_x / t_y as in the forward: cells outside the lengths contribute nothing (whatever grad_value
+    holds there), frames >= t_y and tokens >= t_x get 0.0.  grad_scale [B]: grad_value[b] is read as
+    grad_scale[b] * grad_value[b] (forward_sum()'s stored gradient with a per-utterance cotangent, no scaling pass).
+    Deterministic (no atomics).  Asynchronous on the current stream."""
+    for t, name in ((z, "z"), (mean, "mean"), (logstd, "logstd"), (grad_value, "grad_value")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{name} must be a [B,C,T] tensor" if name != "grad_value"
+                             else "grad_value must be a [B,T_text,T_mel] tensor")
+    B, C, Ty = z.shape
+    B2, C2, Tx = mean.shape
+    if B2 != B or C2 != C:
+        raise ValueError(f"z {tuple(z.shape)} and mean {tuple(mean.shape)} disagree in B or C")
+    if tuple(logstd.shape) != tuple(mean.shape):
+        raise ValueError(f"logstd {tuple(logstd.shape)} must have mean's shape {tuple(mean.shape)}")
+    if C < 1:
+        raise ValueError("C must be at least 1")
+    if tuple(grad_value.shape) != (B, Tx, Ty):
+        raise ValueError(f"grad_value {tuple(grad_value.shape)} must be [B,T_text,T_mel] = {(B, Tx, Ty)}")
+    if not (need_z or need_mean or need_logstd):
+        raise ValueError("at least one of need_z, need_mean, need_logstd must be set")
+    for t, name in ((grad_value, "grad_value"), (z, "z"), (mean, "mean"), (logstd, "logstd")):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a GPU tensor")
+    dev = z.device
+    if mean.device != dev or logstd.device != dev or grad_value.device != dev:
+        raise ValueError("grad_value, z, mean and logstd must be on the same device")
+    for t, name in ((t_x, "t_x"), (t_y, "t_y"), (grad_scale, "grad_scale")):
+        if t is not None and t.numel() != B:
+            raise ValueError(f"{name} must have one entry per utterance")
+    _lib.require_gpu()
+    with torch.no_grad(), torch.cuda.device(dev):
+        zc, mc, sc = _f32(z), _f32(mean), _f32(logstd)
+        g, ld = _grad_layout(grad_value, B, Tx, Ty)
+        if t_x is not None:
+            t_x = t_x.to(device=dev, dtype=torch.int32).contiguous()
+        if t_y is not None:
+            t_y = t_y.to(device=dev, dtype=torch.int32).contiguous()
+        if grad_scale is not None:
+            grad_scale = grad_scale.detach().to(device=dev, dtype=torch.float32).contiguous()
+        dz = torch.empty((B, C, Ty), dtype=torch.float32, device=dev) if need_z else None
+        dm = torch.empty((B, C, Tx), dtype=torch.float32, device=dev) if need_mean else None
+        ds = torch.empty((B, C, Tx), dtype=torch.float32, device=dev) if need_logstd else None
+        if B == 0 or Tx == 0 or Ty == 0:
+            for t in (dz, dm, ds):
+                if t is not None:
+                    t.zero_()
+            return dz, dm, ds
+        lib = _lib.load()
+        nws = lib.aligner_gauss_logp_backward_workspace_bytes(B, C, Tx, Ty)
+        ws = _workspaces.get(dev, max(nws, 1))
+        _lib.check(lib.aligner_gauss_logp_backward_f32(
+            g.data_ptr(), ld, None if grad_scale is None else grad_scale.data_ptr(), zc.data_ptr(), mc.data_ptr(),
+            sc.data_ptr(), None if t_x is None else t_x.data_ptr(), None if t_y is None else t_y.data_ptr(),
+            None if dz is None else dz.data_ptr(), None if dm is None else dm.data_ptr(),
+            None if ds is None else ds.data_ptr(), ws.data_ptr(), ws.numel(), B, C, Tx, Ty,
+            torch.cuda.current_stream(dev).cuda_stream))
+    return dz, dm, ds
+
+
+def _typed(t: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
+    return None if t is None else t.to(like.dtype)
+
+
+class _GaussianLogp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, mean, logstd, t_x, t_y, pitched):
+        ctx.save_for_backward(z, mean, logstd)              # the inputs only: the value is not needed for its gradient
+        ctx.lengths = (t_x, t_y)
+        return gaussian_logp(z, mean, logstd, t_x, t_y, pitched=pitched)
+
+    @staticmethod
+    def backward(ctx, g):
+        z, mean, logstd = ctx.saved_tensors
+        nz, nm, ns = ctx.needs_input_grad[:3]
+        if g is None or not (nz or nm or ns):
+            return None, None, None, None, None, None
+        t_x, t_y = ctx.lengths
+        dz, dm, ds = gaussian_logp_backward(g, z, mean, logstd, t_x, t_y, need_z=nz, need_mean=nm, need_logstd=ns)
+        return _typed(dz, z), _typed(dm, mean), _typed(ds, logstd), None, None, None
+
+
+class _GaussianForwardSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, mean, logstd, t_x, t_y, blank_logprob, zero_infinity):
+        need = any(ctx.needs_input_grad[:3])
+        value = gaussian_logp(z, mean, logstd, t_x, t_y)
+        loss, grad = forward_sum(value, t_x, t_y, want_grad=need, blank_logprob=blank_logprob)
+        del value
+        if zero_infinity:
+            dead = torch.isinf(loss)
+            loss = torch.where(dead, torch.zeros_like(loss), loss)
+            # an utterance without an alignment: zero gradients whatever forward_sum left in its block of G
+            t_x = torch.where(dead, torch.zeros_like(dead, dtype=torch.int32),
+                              torch.as_tensor(t_x).to(device=loss.device, dtype=torch.int32))
+        if need:
+            ctx.save_for_backward(z, mean, logstd, grad)    # z, m, s and G: no other [B,T_text,T_mel] tensor is kept
+        ctx.lengths = (t_x, t_y)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        nz, nm, ns = ctx.needs_input_grad[:3]
+        if g_loss is None or not (nz or nm or ns):
+            return (None,) * 7
+        z, mean, logstd, grad = ctx.saved_tensors
+        t_x, t_y = ctx.lengths
+        dz, dm, ds = gaussian_logp_backward(grad, z, mean, logstd, t_x, t_y, grad_scale=g_loss.reshape(-1),
+                                            need_z=nz, need_mean=nm, need_logstd=ns)
+        return _typed(dz, z), _typed(dm, mean), _typed(ds, logstd), None, None, None, None
+
+
+def gaussian_forward_sum_loss(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_x: torch.Tensor,
+                              t_y: torch.Tensor, *, blank_logprob: Optional[float] = None, reduction: str = "mean",
+                              zero_infinity: bool = False, length_normalize: bool = False) -> torch.Tensor:
+    """-log of the likelihood of z summed over ALL monotonic alignments of the tokens' Gaussians -- AlignTTS's
+    mixture-density alignment loss (blank_logprob=None, the plain monotonic form), the soft replacement or warm start of
+    the hard search in Glow-TTS / VITS -- as one autograd function: gaussian_logp() -> forward_sum() forward, one
+    gaussian_logp_backward() backward whose grad_scale carries the per-utterance cotangent (the incoming gradient, the
+    1/B of "mean", 1/t_x with length_normalize, 0 for an utterance zeroed by zero_infinity).  Only z, mean, logstd and
+    forward_sum's gradient tensor are kept for backward.  The options are forward_sum_loss()'s; gradients come back in
+    each input's dtype."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+    if t_x is None or t_y is None:
+        raise ValueError("gaussian_forward_sum_loss needs the lengths t_x and t_y")
+    loss = _GaussianForwardSum.apply(z, mean, logstd, t_x, t_y, blank_logprob, bool(zero_infinity))
+    if length_normalize:
+        loss = loss / torch.as_tensor(t_x).to(device=loss.device, dtype=loss.dtype).clamp_min(1)
+    if reduction == "mean":
+        return loss.mean()
+    if reduction == "sum":
+        return loss.sum()
+    return loss

@@ -42,7 +42,8 @@ extern "C" {
  *    aligner_conv1d_backward_weight_f32 / aligner_conv1d_backward_workspace_bytes; and the hard half of the training
  *    objective -- aligner_segment_reduce_f32, aligner_bin_loss, aligner_bin_loss_grad_f32; and the hard search with
  *    optional pauses between tokens -- aligner_pausepath / aligner_pausepath_workspace_bytes; and the Glow-TTS / VITS
- *    log-likelihood front end -- aligner_gauss_logp / aligner_gauss_logp_workspace_bytes; and their likelihood loss on
+ *    log-likelihood front end -- aligner_gauss_logp / aligner_gauss_logp_workspace_bytes, its gradient
+ *    aligner_gauss_logp_backward_f32 / aligner_gauss_logp_backward_workspace_bytes; and their likelihood loss on
  *    the hard path -- aligner_gauss_nll_f32 / aligner_gauss_nll_workspace_bytes; and Gaussian upsampling with its
  *    gradient -- aligner_gauss_upsample_f32 / aligner_gauss_upsample_backward_f32 and their *_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
@@ -373,7 +374,8 @@ int aligner_softattn_backward_f32(const float *keys_dev, const float *queries_de
  * cores with every fp32 operand split in two bf16 halves (hi*hi + hi*lo + lo*hi, fp32 accumulate: ~2^-16 relative per
  * product).  The expanded terms cancel where z ~ mean and the deviation is small, so the error is relative to the
  * magnitude of what is summed, S = sum_c (1/2 z^2 w + |z mean| w + 1/2 mean^2 w + |logstd| + 1/2 ln 2pi), w = exp(-2
- * logstd): |value - exact| <= 2^-14 S.  No atomics: the same bits on every call.  No gradient.
+ * logstd): |value - exact| <= 2^-14 S.  No atomics: the same bits on every call.  Its gradient:
+ * aligner_gauss_logp_backward_f32.
  * Domain: 1 <= C <= 256 (any C: the contraction is padded with zeros inside the kernel), Tx <= 1024, any Ty, B <= 65535,
  * Tx*ld_value < 2^29: ALIGNER_EDOM beyond; ALIGNER_EINVAL for a null pointer, a shape below 1, ld_value < Ty or a dtype
  * other than F32 / BF16.  Arguments are validated before any HIP call.  Two launches (prepare, main), asynchronous.
@@ -384,6 +386,37 @@ int aligner_gauss_logp(const float *z_dev, const float *mean_dev, const float *l
                        void *value_out_dev, int value_dtype, int ld_value,
                        void *workspace_dev, size_t workspace_bytes,
                        int B, int C, int Tx, int Ty, void *stream);
+
+/*
+ * The vector-Jacobian product of aligner_gauss_logp: with G = grad_value (the gradient of a loss with respect to value,
+ * e.g. aligner_forward_sum_f32's gradient tensor), cells with i >= t_x[b] or j >= t_y[b] contributing nothing, and
+ * w = exp(-2 logstd),
+ *   R[i] = sum_j G[i,j]   P[c,i] = sum_j G[i,j] z[c,j]   Q[c,i] = sum_j G[i,j] z[c,j]^2
+ *   U[c,j] = sum_i G[i,j] w[c,i]   V[c,j] = sum_i G[i,j] (mean w)[c,i]
+ *   dz = V - z U      dmean = w (P - mean R)      dlogstd = w (Q - 2 mean P + mean^2 R) - R
+ *   grad_value_dev  element [b,i,j] at ((b*Tx + i)*ld_grad + j), fp32; ld_grad == Ty or a row pitch > Ty with rows on
+ *               16-byte boundaries.  Neither a cell outside the lengths nor a pad column is read into any result (a NaN
+ *               there is harmless).
+ *   grad_scale_dev  optional [B] fp32: G[b] is read as grad_scale[b] * G[b] (the cotangent of a per-utterance loss,
+ *               without a scaling pass over G)
+ *   z_dev, mean_dev, logstd_dev, t_xs_dev, t_ys_dev  as for aligner_gauss_logp (the same clamping of the lengths)
+ *   dz_out_dev [B,C,Ty], dmean_out_dev [B,C,Tx], dlogstd_out_dev [B,C,Tx]  fp32, each fully written (frames >= t_y,
+ *               tokens >= t_x and empty utterances: +0.0); each may be NULL, not all three.  A NULL dz skips the
+ *               contraction over tokens, NULL dmean and dlogstd the one over frames.
+ *   workspace_dev  aligner_gauss_logp_backward_workspace_bytes(B,C,Tx,Ty) bytes (0 for a shape that is not supported)
+ * Arithmetic: U, V, P, Q with the forward's three split bf16 products per fp32 product, R in fp32.  Per element
+ * |got - exact| <= 2^-14 S with S the magnitude of what the expanded sums add up.  No atomics, the frame
+ * sweep is split over workgroups by the shape alone and summed in split order: the same bits on every call.
+ * Domain: 1 <= C <= 256, Tx <= 1024, B <= 65535: ALIGNER_EDOM beyond; ALIGNER_EINVAL for a null pointer, no output, a
+ * shape below 1 or a bad ld_grad; ALIGNER_ENOSPC for a workspace that is too small.  Validated before any HIP call.
+ */
+size_t aligner_gauss_logp_backward_workspace_bytes(int B, int C, int Tx, int Ty);
+int aligner_gauss_logp_backward_f32(const float *grad_value_dev, int ld_grad, const float *grad_scale_dev,
+                                    const float *z_dev, const float *mean_dev, const float *logstd_dev,
+                                    const int32_t *t_xs_dev, const int32_t *t_ys_dev,
+                                    float *dz_out_dev, float *dmean_out_dev, float *dlogstd_out_dev,
+                                    void *workspace_dev, size_t workspace_bytes,
+                                    int B, int C, int Tx, int Ty, void *stream);
 
 /*
  * The loss those models train on once the alignment is found: the negative log-likelihood of every latent frame under
