@@ -22,31 +22,9 @@ unsigned long long *g_debug_stamps = nullptr;
 
 // Development switches (aligner_debug_set_option): default from the environment, read once.
 static int env_flag(const char *name) { const char *e = getenv(name); return e && e[0] && e[0] != '0'; }
-int g_opt_fwdsum_one_wave = env_flag("ALIGNER_FWDSUM_ONE_WAVE");
-int g_opt_fwdsum_serial = env_flag("ALIGNER_FWDSUM_SERIAL");
-int g_opt_fwdsum_no_grad_stager = 0;
-int g_opt_gaussnll_rows = 0;
-int g_opt_gaussnll_grid = 0;
-int g_opt_gaussup_full_range = 0;
-int g_opt_softattn_exact = env_flag("ALIGNER_SOFTATTN_EXACT");
-int g_opt_mobo_drop_segment = -1;
-int g_opt_mobo_start_lag = 0;
-int g_opt_mobo_lanes = 0;
-int g_opt_mobo_bwd_general = 0;
-int g_opt_softattn_no_pair = 0;
-int g_opt_softattn_rt_drop_merge = 0;
-int g_opt_softattn_strips = env_flag("ALIGNER_SOFTATTN_STRIPS");
-int g_opt_softattn_split = 0;
-int g_opt_conv_narrow_ft = 0;
-int g_opt_conv_no_ring = 0;
-int g_opt_conv_no_fuse = 0;
-int g_opt_conv_split_always = env_flag("ALIGNER_CONV_SPLIT_ALWAYS");
-int g_opt_maxpath_no_split_walk = 0;
-int g_opt_maxpath_zero_blocks = 0;
-int g_opt_maxpath_no_mask_verify = 0;
-int g_opt_maxpath_no_optimistic_mask = 0;
-int g_opt_mobo_full_chain = 0;
-int g_opt_mobo_stamp_wave = 0;
+#define ALIGNER_DEFINE_OPTION(name, initial, what) int g_opt_##name = initial;
+ALIGNER_DEBUG_OPTIONS(ALIGNER_DEFINE_OPTION)
+#undef ALIGNER_DEFINE_OPTION
 
 hipError_t ensure_dynamic_lds(const void *kernel, size_t bytes) {
     if (bytes <= 64 * 1024) return hipSuccess;
@@ -119,31 +97,10 @@ void aligner_debug_set_stamps(void *stamps_dev) {
 
 int aligner_debug_set_option(const char *name, int value) {
     if (!name) return aligner::fail(ALIGNER_EINVAL, "null option name");
-    if (std::strcmp(name, "fwdsum_one_wave") == 0) { aligner::g_opt_fwdsum_one_wave = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "fwdsum_no_grad_stager") == 0) { aligner::g_opt_fwdsum_no_grad_stager = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "gaussnll_rows") == 0) { aligner::g_opt_gaussnll_rows = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "gaussnll_grid") == 0) { aligner::g_opt_gaussnll_grid = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "gaussup_full_range") == 0) { aligner::g_opt_gaussup_full_range = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "fwdsum_serial") == 0) { aligner::g_opt_fwdsum_serial = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "softattn_exact") == 0) { aligner::g_opt_softattn_exact = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "mobo_start_lag") == 0) { aligner::g_opt_mobo_start_lag = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "mobo_lanes") == 0) { aligner::g_opt_mobo_lanes = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "mobo_stamp_wave") == 0) { aligner::g_opt_mobo_stamp_wave = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "mobo_full_chain") == 0) { aligner::g_opt_mobo_full_chain = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "softattn_split") == 0) { aligner::g_opt_softattn_split = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "conv_narrow_ft") == 0) { aligner::g_opt_conv_narrow_ft = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "conv_no_ring") == 0) { aligner::g_opt_conv_no_ring = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "conv_no_fuse") == 0) { aligner::g_opt_conv_no_fuse = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "conv_split_always") == 0) { aligner::g_opt_conv_split_always = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "maxpath_no_optimistic_mask") == 0) { aligner::g_opt_maxpath_no_optimistic_mask = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "maxpath_no_mask_verify") == 0) { aligner::g_opt_maxpath_no_mask_verify = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "maxpath_zero_blocks") == 0) { aligner::g_opt_maxpath_zero_blocks = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "maxpath_no_split_walk") == 0) { aligner::g_opt_maxpath_no_split_walk = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "softattn_strips") == 0) { aligner::g_opt_softattn_strips = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "softattn_rt_drop_merge") == 0) { aligner::g_opt_softattn_rt_drop_merge = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "softattn_no_pair") == 0) { aligner::g_opt_softattn_no_pair = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "mobo_bwd_general") == 0) { aligner::g_opt_mobo_bwd_general = value; return ALIGNER_OK; }
-    if (std::strcmp(name, "mobo_drop_segment") == 0) { aligner::g_opt_mobo_drop_segment = value; return ALIGNER_OK; }
+#define ALIGNER_SET_OPTION(opt, initial, what) \
+    if (std::strcmp(name, #opt) == 0) { aligner::g_opt_##opt = value; return ALIGNER_OK; }
+    ALIGNER_DEBUG_OPTIONS(ALIGNER_SET_OPTION)
+#undef ALIGNER_SET_OPTION
     return aligner::fail(ALIGNER_EINVAL, "unknown option '%s'", name);
 }
 

@@ -43,31 +43,38 @@ int device_cu_count();                // compute units of the current device (ca
 
 // development aid shared by the kernel files (aligner_debug_set_stamps)
 extern unsigned long long *g_debug_stamps;
-extern int g_opt_softattn_exact;       // "softattn_exact": always the exact-product similarity kernel
-extern int g_opt_mobo_start_lag;       // "mobo_start_lag": rows a position segment lets its predecessor get ahead before it starts (default 0)
-extern int g_opt_mobo_stamp_wave;      // "mobo_stamp_wave": development, the wave whose first lane takes the gradient chain's stamps
-extern int g_opt_mobo_full_chain;      // "mobo_full_chain": testing, the search without log_alpha on the full (sum + max) chain kernel
-extern int g_opt_conv_narrow_ft;      // "conv_narrow_ft": testing, frame tiles (8, 4, 2) per workgroup of the narrow conv kernel (0: the plan's choice)
-extern int g_opt_conv_no_ring;        // "conv_no_ring": A-B / testing, a k = 1 layer with many input chunks stages them all at once (conv_narrow_kernel)
-extern int g_opt_maxpath_no_optimistic_mask;   // "maxpath_no_optimistic_mask": A-B / testing, the strict mask is verified by a pass in front of the search, not by the zero workgroups beside it
-extern int g_opt_maxpath_no_mask_verify;   // "maxpath_no_mask_verify": A-B / testing, a strict mask is always multiplied in (no verification pass)
-extern int g_opt_maxpath_zero_blocks;      // "maxpath_zero_blocks": development, zero workgroups of the two-workgroup search launch (0: all idle CUs)
-extern int g_opt_maxpath_no_split_walk;   // "maxpath_no_split_walk": A-B / testing, the two-workgroup search with one walker (the second half) for all rows
-extern int g_opt_conv_no_fuse;        // "conv_no_fuse": testing / A-B, a stack's trailing narrow layers as separate kernels instead of conv_narrow_fused_kernel
-extern int g_opt_conv_split_always;    // "conv_split_always": narrow layers never stage fp32 themselves (A/B, tests)
-extern int g_opt_softattn_split;       // "softattn_split": development, waves per strip of the row-group form (2, 4; 1: at most 2; 0: the launch's choice)
-extern int g_opt_softattn_strips;      // "softattn_strips": A/B / testing, the one-row-group similarity kernel in its strip-per-wave form (softattn_kernel) instead of the row-tile form
-extern int g_opt_softattn_rt_drop_merge;   // "softattn_rt_drop_merge": testing, the row-tile similarity kernel's loader never publishes a strip's normaliser
-extern int g_opt_softattn_no_pair;     // "softattn_no_pair": testing, the similarity kernel's row-group form with one wave per strip only
-extern int g_opt_mobo_bwd_general;     // "mobo_bwd_general": testing, the gradient's chain in its general (one exp2 per term) form
-extern int g_opt_mobo_lanes;           // "mobo_lanes": development, lanes per position in the split form (0: the plan's choice)
-extern int g_opt_mobo_drop_segment;    // "mobo_drop_segment": testing, that position segment never publishes (-1: off)
-extern int g_opt_gaussnll_rows;         // "gaussnll_rows": A-B / testing, rows per wave and pass of gauss_nll_kernel (1, 2, 4; never above what LDS allows at the T_text; 0: the launch's choice)
-extern int g_opt_gaussnll_grid;         // "gaussnll_grid": testing, at most this many workgroups per utterance in gauss_nll_kernel's launch, so that a workgroup takes several row groups (0: the launch's choice)
-extern int g_opt_gaussup_full_range;    // "gaussup_full_range": A-B / testing, every frame tile of the Gaussian upsampling kernels takes the full token range [0, t_x) (the path of centres that are out of order)
-extern int g_opt_fwdsum_no_grad_stager; // "fwdsum_no_grad_stager": A-B / testing, the gradient-making backward kernel with its compiler-scheduled stager
-extern int g_opt_fwdsum_serial;        // "fwdsum_serial": forward then backward sweep, never side by side (A/B, tests)
-extern int g_opt_fwdsum_one_wave;      // aligner_debug_set_option("fwdsum_one_wave", ...); default: env, read once
+// The debug options (aligner_debug_set_option), one line each: name, default, what it does.  The declarations below,
+// the definitions (api.cpp: the only place that evaluates the defaults; env_flag reads the environment once) and the
+// lookup by name in aligner_debug_set_option are all generated from this list.
+#define ALIGNER_DEBUG_OPTIONS(X) \
+    X(softattn_exact, env_flag("ALIGNER_SOFTATTN_EXACT"), "always the exact-product similarity kernel") \
+    X(mobo_start_lag, 0, "rows a position segment lets its predecessor get ahead before it starts (default 0)") \
+    X(mobo_stamp_wave, 0, "development, the wave whose first lane takes the gradient chain's stamps") \
+    X(mobo_full_chain, 0, "testing, the search without log_alpha on the full (sum + max) chain kernel") \
+    X(conv_narrow_ft, 0, "testing, frame tiles (8, 4, 2) per workgroup of the narrow conv kernel (0: the plan's choice)") \
+    X(conv_no_ring, 0, "A-B / testing, a k = 1 layer with many input chunks stages them all at once (conv_narrow_kernel)") \
+    X(maxpath_no_optimistic_mask, 0, "A-B / testing, the strict mask is verified by a pass in front of the search, not by the zero workgroups beside it") \
+    X(maxpath_no_mask_verify, 0, "A-B / testing, a strict mask is always multiplied in (no verification pass)") \
+    X(maxpath_zero_blocks, 0, "development, zero workgroups of the two-workgroup search launch (0: all idle CUs)") \
+    X(maxpath_no_split_walk, 0, "A-B / testing, the two-workgroup search with one walker (the second half) for all rows") \
+    X(conv_no_fuse, 0, "testing / A-B, a stack's trailing narrow layers as separate kernels instead of conv_narrow_fused_kernel") \
+    X(conv_split_always, env_flag("ALIGNER_CONV_SPLIT_ALWAYS"), "narrow layers never stage fp32 themselves (A/B, tests)") \
+    X(softattn_split, 0, "development, waves per strip of the row-group form (2, 4; 1: at most 2; 0: the launch's choice)") \
+    X(softattn_strips, env_flag("ALIGNER_SOFTATTN_STRIPS"), "A/B / testing, the one-row-group similarity kernel in its strip-per-wave form (softattn_kernel) instead of the row-tile form") \
+    X(softattn_rt_drop_merge, 0, "testing, the row-tile similarity kernel's loader never publishes a strip's normaliser") \
+    X(softattn_no_pair, 0, "testing, the similarity kernel's row-group form with one wave per strip only") \
+    X(mobo_bwd_general, 0, "testing, the gradient's chain in its general (one exp2 per term) form") \
+    X(mobo_lanes, 0, "development, lanes per position in the split form (0: the plan's choice)") \
+    X(mobo_drop_segment, -1, "testing, that position segment never publishes (-1: off)") \
+    X(gaussnll_rows, 0, "A-B / testing, rows per wave and pass of gauss_nll_kernel (1, 2, 4; never above what LDS allows at the T_text; 0: the launch's choice)") \
+    X(gaussnll_grid, 0, "testing, at most this many workgroups per utterance in gauss_nll_kernel's launch, so that a workgroup takes several row groups (0: the launch's choice)") \
+    X(gaussup_full_range, 0, "A-B / testing, every frame tile of the Gaussian upsampling kernels takes the full token range [0, t_x) (the path of centres that are out of order)") \
+    X(fwdsum_no_grad_stager, 0, "A-B / testing, the gradient-making backward kernel with its compiler-scheduled stager") \
+    X(fwdsum_serial, env_flag("ALIGNER_FWDSUM_SERIAL"), "forward then backward sweep, never side by side (A/B, tests)") \
+    X(fwdsum_one_wave, env_flag("ALIGNER_FWDSUM_ONE_WAVE"), "A/B / testing, always the one-sweeping-wave forward-sum kernels (the systolic ones never)")
+#define ALIGNER_DECLARE_OPTION(name, initial, what) extern int g_opt_##name;
+ALIGNER_DEBUG_OPTIONS(ALIGNER_DECLARE_OPTION)
+#undef ALIGNER_DECLARE_OPTION
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

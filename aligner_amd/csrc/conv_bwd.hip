@@ -19,10 +19,9 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int CW_TILE = 128, CW_CHUNK = 32, CW_P = CW_CHUNK + 1, CW_PER = CW_TILE * CW_CHUNK / 256;
 

@@ -44,13 +44,12 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 cg_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float cg_f32x4;
 typedef unsigned __attribute__((ext_vector_type(4))) cg_u32x4;
-typedef __attribute__((ext_vector_type(16))) float cg_f32x16;
 
 constexpr int CG_CH = 32;            // input channels per chunk (one k-step of v_mfma_f32_16x16x32_bf16)
 constexpr int CG_TO = 128;           // output channels per workgroup (4 waves x 2 tiles of 16)
@@ -75,14 +74,6 @@ static ConvGemmLayout conv_gemm_layout(int B, int Cin, int Cout, int T, int K) {
     return L;
 }
 
-__device__ __forceinline__ float and_maskf(float v, unsigned m) {            // v or +0.0 without a branch
-    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & m);
-}
-__device__ __forceinline__ void cg_split(float v, __bf16 &hi, __bf16 &lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
-}
-
 // weights -> fragment order.  B operand of the MFMA (k = input channel, n = output channel): lane l holds
 // w[o = 16*tile + (l & 15)][i = 32*chunk + 8*(l >> 4) + j][tap], j = 0..7.
 // tr: w is the weight of the layer this one is the transpose of ([Cin][Cout][K]; w'[o][i][tap] = w[i][o][K-1-tap]: the
@@ -98,13 +89,13 @@ __global__ __launch_bounds__(256) void conv_gemm_wprep_kernel(const float *__res
     const int lane = idx & 63, tile = (idx >> 6) % (cpad / 16), ct = (idx >> 6) / (cpad / 16);
     const int tap = ct % K, ch = ct / K;
     const int o = 16 * tile + (lane & 15);
-    cg_bf16x8 hv, lv;
+    bf16x8 hv, lv;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int i = CG_CH * ch + 8 * (lane >> 4) + j;
         const float v = (o < Cout && i < Cin) ? w[cg_widx(o, i, tap, Cout, Cin, K, tr)] : 0.f;
         __bf16 hh, ll;
-        cg_split(v, hh, ll);
+        split_bf16(v, hh, ll);
         hv[j] = hh;
         lv[j] = ll;
     }
@@ -147,11 +138,11 @@ __global__ __launch_bounds__(256) void conv_split_kernel(const float *__restrict
     for (int u = 0; u < CS_U; ++u) {
         const size_t idx = idx0 + (size_t)u * 256;
         if (idx >= total) break;
-        cg_bf16x8 hv, lv;
+        bf16x8 hv, lv;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             __bf16 hh, ll;
-            cg_split(in[u] ? v[u][j] : 0.f, hh, ll);
+            split_bf16(in[u] ? v[u][j] : 0.f, hh, ll);
             hv[j] = hh;
             lv[j] = ll;
         }
@@ -249,7 +240,7 @@ __device__ __forceinline__ void cg_store_split(const ConvGemmParams &p, const cg
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int o = ob + r;
-                bv[r] = and_maskf(p.bias[o < p.Cout ? o : p.Cout - 1], o < p.Cout ? ~0u : 0u);
+                bv[r] = and_mask(p.bias[o < p.Cout ? o : p.Cout - 1], o < p.Cout ? ~0u : 0u);
             }
         }
         // image [b][chunk = ob / 32][quarter = (ob % 32) / 8][slot] of 16 bytes; this lane's half at + 8 * ((ob % 8) / 4)
@@ -264,9 +255,9 @@ __device__ __forceinline__ void cg_store_split(const ConvGemmParams &p, const cg
             for (int r = 0; r < 4; ++r) {
                 float v = acc[a][n][r] + bv[r];
                 if (p.relu) v = fmaxf(v, 0.f);
-                v = and_maskf(v, (f < p.T && ob + r < p.Cout) ? ~0u : 0u);
+                v = and_mask(v, (f < p.T && ob + r < p.Cout) ? ~0u : 0u);
                 __bf16 hh, ll;
-                cg_split(v, hh, ll);
+                split_bf16(v, hh, ll);
                 hv[r] = hh;
                 lv[r] = ll;
             }
@@ -279,7 +270,7 @@ __device__ __forceinline__ void cg_store_split(const ConvGemmParams &p, const cg
 
 // 6 MFMAs of one (frame tile, output tile pair): products lo*hi, hi*lo, hi*hi; SPLIT swaps the operands' roles
 template <bool SPLIT>
-__device__ __forceinline__ cg_f32x4 cg_mfma(cg_bf16x8 x, cg_bf16x8 w, cg_f32x4 c) {
+__device__ __forceinline__ cg_f32x4 cg_mfma(bf16x8 x, bf16x8 w, cg_f32x4 c) {
     return SPLIT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, w, c, 0, 0, 0);
 }
 
@@ -359,24 +350,24 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGemmParams p) {
         // fragments one frame tile ahead of their MFMAs, ACROSS the taps of the chunk (left alone, hipcc issues a tile's two
         // reads and waits for the first at once: an LDS round trip per six MFMAs; with the look-ahead restarted per tap a
         // round trip per tap was exposed: three per chunk)
-        cg_bf16x8 xh = *reinterpret_cast<const cg_bf16x8 *>(st);
-        cg_bf16x8 xl = *reinterpret_cast<const cg_bf16x8 *>(st + (4 * LROW) * 16);
+        bf16x8 xh = *reinterpret_cast<const bf16x8 *>(st);
+        bf16x8 xl = *reinterpret_cast<const bf16x8 *>(st + (4 * LROW) * 16);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                  // (the chunk's first reads: a group of their own)
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
             // W[t] of this chunk is the oldest operation in flight; younger: the other taps (4 each), the staging pieces
             cg_wait4<NP + 4 * (KT - 1)>(W[t][0], W[t][1], W[t][2], W[t][3]);
-            const cg_bf16x8 wh0 = __builtin_bit_cast(cg_bf16x8, W[t][0]), wl0 = __builtin_bit_cast(cg_bf16x8, W[t][1]);
-            const cg_bf16x8 wh1 = __builtin_bit_cast(cg_bf16x8, W[t][2]), wl1 = __builtin_bit_cast(cg_bf16x8, W[t][3]);
+            const bf16x8 wh0 = __builtin_bit_cast(bf16x8, W[t][0]), wl0 = __builtin_bit_cast(bf16x8, W[t][1]);
+            const bf16x8 wh1 = __builtin_bit_cast(bf16x8, W[t][2]), wl1 = __builtin_bit_cast(bf16x8, W[t][3]);
 #pragma unroll
             for (int n = 0; n < FT; ++n) {
-                cg_bf16x8 nh = xh, nl = xl;
+                bf16x8 nh = xh, nl = xl;
                 if (n + 1 < FT) {
-                    nh = *reinterpret_cast<const cg_bf16x8 *>(st + (16 * (n + 1) + t) * 16);
-                    nl = *reinterpret_cast<const cg_bf16x8 *>(st + (4 * LROW + 16 * (n + 1) + t) * 16);
+                    nh = *reinterpret_cast<const bf16x8 *>(st + (16 * (n + 1) + t) * 16);
+                    nl = *reinterpret_cast<const bf16x8 *>(st + (4 * LROW + 16 * (n + 1) + t) * 16);
                 } else if (t + 1 < KT) {                                     // the next tap's first tile
-                    nh = *reinterpret_cast<const cg_bf16x8 *>(st + (t + 1) * 16);
-                    nl = *reinterpret_cast<const cg_bf16x8 *>(st + (4 * LROW + t + 1) * 16);
+                    nh = *reinterpret_cast<const bf16x8 *>(st + (t + 1) * 16);
+                    nl = *reinterpret_cast<const bf16x8 *>(st + (4 * LROW + t + 1) * 16);
                 }
                 acc[0][n] = cg_mfma<SPLIT>(xl, wh0, acc[0][n]);
                 acc[1][n] = cg_mfma<SPLIT>(xl, wh1, acc[1][n]);
@@ -484,19 +475,19 @@ __device__ __forceinline__ void cn_step(CnRing<NT, RD> &R, const unsigned char *
         const int ps = R.phys(s);
         const int c = ps / KT, t = ps - c * KT;
         const unsigned char *st = xl + (size_t)c * CHSLOT * 16 + (unsigned)((lane >> 4) * LROW + (lane & 15)) * 16u + t * 16;
-        const cg_bf16x8 wh0 = __builtin_bit_cast(cg_bf16x8, R.W[I][0]), wl0 = __builtin_bit_cast(cg_bf16x8, R.W[I][1]);
-        const cg_bf16x8 wh1 = __builtin_bit_cast(cg_bf16x8, R.W[I][2 * NT - 2]), wl1 = __builtin_bit_cast(cg_bf16x8, R.W[I][2 * NT - 1]);
+        const bf16x8 wh0 = __builtin_bit_cast(bf16x8, R.W[I][0]), wl0 = __builtin_bit_cast(bf16x8, R.W[I][1]);
+        const bf16x8 wh1 = __builtin_bit_cast(bf16x8, R.W[I][2 * NT - 2]), wl1 = __builtin_bit_cast(bf16x8, R.W[I][2 * NT - 1]);
         // fragments one frame tile ahead of their MFMAs (as in the wide kernel: left alone, hipcc issues a tile's reads and
         // waits for them at once -- an LDS round trip per 3 * NT MFMAs, with one or two waves per SIMD to hide it)
-        cg_bf16x8 xh = *reinterpret_cast<const cg_bf16x8 *>(st);
-        cg_bf16x8 xlo = *reinterpret_cast<const cg_bf16x8 *>(st + (4 * LROW) * 16);
+        bf16x8 xh = *reinterpret_cast<const bf16x8 *>(st);
+        bf16x8 xlo = *reinterpret_cast<const bf16x8 *>(st + (4 * LROW) * 16);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
 #pragma unroll
         for (int n = 0; n < FTW; ++n) {
-            cg_bf16x8 nh = xh, nl = xlo;
+            bf16x8 nh = xh, nl = xlo;
             if (n + 1 < FTW) {
-                nh = *reinterpret_cast<const cg_bf16x8 *>(st + (16 * (n + 1)) * 16);
-                nl = *reinterpret_cast<const cg_bf16x8 *>(st + (4 * LROW + 16 * (n + 1)) * 16);
+                nh = *reinterpret_cast<const bf16x8 *>(st + (16 * (n + 1)) * 16);
+                nl = *reinterpret_cast<const bf16x8 *>(st + (4 * LROW + 16 * (n + 1)) * 16);
             }
             acc[0][n] = cg_mfma<WA>(xlo, wh0, acc[0][n]);
             if (NT == 2) acc[NT - 1][n] = cg_mfma<WA>(xlo, wh1, acc[NT - 1][n]);
@@ -578,11 +569,11 @@ __device__ __forceinline__ void cn_stage_f32(const float *__restrict__ x, int Ci
                 const int sl = it % LROW, cq = it / LROW;
                 const int t = f0 + sl - HALO;
                 const bool in = t >= 0 && t < T;
-                cg_bf16x8 hv, lv;
+                bf16x8 hv, lv;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     __bf16 hh, ll;
-                    cg_split((in && 8 * cq + j < Cin) ? v[u][j] : 0.f, hh, ll);
+                    split_bf16((in && 8 * cq + j < Cin) ? v[u][j] : 0.f, hh, ll);
                     hv[j] = hh;
                     lv[j] = ll;
                 }
@@ -742,7 +733,7 @@ __device__ __forceinline__ void cg_store_lds(unsigned char *dst, int nch_next, c
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int o = ob + r;
-                bv[r] = and_maskf(L.bias[o < L.Cout ? o : L.Cout - 1], o < L.Cout ? ~0u : 0u);
+                bv[r] = and_mask(L.bias[o < L.Cout ? o : L.Cout - 1], o < L.Cout ? ~0u : 0u);
             }
         }
         const unsigned keep[4] = {ob + 0 < L.Cout ? ~0u : 0u, ob + 1 < L.Cout ? ~0u : 0u, ob + 2 < L.Cout ? ~0u : 0u,
@@ -756,9 +747,9 @@ __device__ __forceinline__ void cg_store_lds(unsigned char *dst, int nch_next, c
             for (int r = 0; r < 4; ++r) {
                 float v = acc[a][n][r] + bv[r];
                 if (L.relu) v = fmaxf(v, 0.f);
-                v = and_maskf(v, keep[r] & fin);
+                v = and_mask(v, keep[r] & fin);
                 __bf16 hh, ll;
-                cg_split(v, hh, ll);
+                split_bf16(v, hh, ll);
                 hv[r] = hh;
                 lv[r] = ll;
             }
@@ -907,13 +898,13 @@ __global__ __launch_bounds__(256) void conv_prep_kernel(const float *__restrict_
     if (idx >= nfrag) return;
     const int h = idx & 1, o = (idx >> 1) % cpad, ct = (idx >> 1) / cpad;
     const int tap = ct % K, ch = ct / K;
-    cg_bf16x8 hv, lv;
+    bf16x8 hv, lv;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
         const int i = 16 * ch + 8 * h + jj;
         const float v = (o < Cout && i < Cin) ? w[cg_widx(o, i, tap, Cout, Cin, K, tr)] : 0.f;
         __bf16 hh, ll;
-        cg_split(v, hh, ll);
+        split_bf16(v, hh, ll);
         hv[jj] = hh;
         lv[jj] = ll;
     }
@@ -961,7 +952,7 @@ __global__ __launch_bounds__(WO * WT * 64) void conv1d_prepared_kernel(const flo
     const int o0 = blockIdx.y * TO, t0 = blockIdx.x * TT;
     const int wo = (wave / WT) * (32 * AO), wt = (wave % WT) * (32 * AT);
     const float *xb = x + (size_t)b * Cin * T;
-    cg_f32x16 acc[AO][AT];
+    f32x16 acc[AO][AT];
 #pragma unroll
     for (int a = 0; a < AO; ++a)
 #pragma unroll
@@ -1013,7 +1004,7 @@ __global__ __launch_bounds__(WO * WT * 64) void conv1d_prepared_kernel(const flo
                         const cg_f32x4 v = *reinterpret_cast<const cg_f32x4 *>(xb + (size_t)(i < Cin ? i : Cin - 1) * T + tc);
                         const unsigned mk = (in && i < Cin) ? ~0u : 0u;
                         cg_f32x4 mv;
-                        mv.x = and_maskf(v.x, mk); mv.y = and_maskf(v.y, mk); mv.z = and_maskf(v.z, mk); mv.w = and_maskf(v.w, mk);
+                        mv.x = and_mask(v.x, mk); mv.y = and_mask(v.y, mk); mv.z = and_mask(v.z, mk); mv.w = and_mask(v.w, mk);
                         R.xq[j][jj] = mv;
                     }
                 }
@@ -1032,17 +1023,17 @@ __global__ __launch_bounds__(WO * WT * 64) void conv1d_prepared_kernel(const flo
                 for (int jj = 0; jj < 8; ++jj) {
                     const int i = i0 + 8 * h + jj;
                     const float v = xb[(size_t)(i < Cin ? i : Cin - 1) * T + tc];
-                    R.xr[j][jj] = and_maskf(v, (i < Cin && t >= 0 && t < T) ? ~0u : 0u);
+                    R.xr[j][jj] = and_mask(v, (i < Cin && t >= 0 && t < T) ? ~0u : 0u);
                 }
             }
         }
     };
     auto pack_split = [&](const float (&r)[8], uint4 &hi, uint4 &lo) {
-        cg_bf16x8 h, l;
+        bf16x8 h, l;
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
             __bf16 hh, ll;
-            cg_split(r[jj], hh, ll);
+            split_bf16(r[jj], hh, ll);
             h[jj] = hh;
             l[jj] = ll;
         }
@@ -1054,18 +1045,18 @@ __global__ __launch_bounds__(WO * WT * 64) void conv1d_prepared_kernel(const flo
 #pragma unroll
         for (int st = 0; st < SUB * K; ++st) {
             const int sub = st / K, tap = st - sub * K;
-            cg_bf16x8 ah[AO], al[AO], bh[AT], bl[AT];
+            bf16x8 ah[AO], al[AO], bh[AT], bl[AT];
 #pragma unroll
             for (int a = 0; a < AO; ++a) {
                 const int idx = sub * WN1 + half * (K * TO) + tap * TO + wo + 32 * a + l31;       // [sub][channel half][tap][out channel]
-                ah[a] = __builtin_bit_cast(cg_bf16x8, Whi[idx]);
-                al[a] = __builtin_bit_cast(cg_bf16x8, Wlo[idx]);
+                ah[a] = __builtin_bit_cast(bf16x8, Whi[idx]);
+                al[a] = __builtin_bit_cast(bf16x8, Wlo[idx]);
             }
 #pragma unroll
             for (int c = 0; c < AT; ++c) {
                 const int idx = sub * XN1 + half * XF + (wt + 32 * c + l31 + tap - HALO + F0);     // [sub][channel half][frame]
-                bh[c] = __builtin_bit_cast(cg_bf16x8, Xhi[idx]);
-                bl[c] = __builtin_bit_cast(cg_bf16x8, Xlo[idx]);
+                bh[c] = __builtin_bit_cast(bf16x8, Xhi[idx]);
+                bl[c] = __builtin_bit_cast(bf16x8, Xlo[idx]);
             }
 #pragma unroll
             for (int a = 0; a < AO; ++a)

@@ -37,6 +37,7 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
 
@@ -115,9 +116,14 @@ __device__ __forceinline__ void fs_store_logz(const FwdSumParams &p, int b, doub
 }
 __device__ __forceinline__ bool fs_has_alignment(double logz) { return logz > (double)FS_NEG_INF; }
 
-// workgroup barrier for LDS traffic only: __syncthreads() would also wait for the stagers' global
-// stores (vmcnt(0)), a memory round trip per tile
-__device__ __forceinline__ void fs_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// `int tx, ty`: utterance b's lengths, clamped from above only (the lengths are always given, and a length below 1 fails
+// the `tx >= 1 && tx <= ty` test that follows: "no alignment").  A macro, not a function: every function form tried
+// (p by reference or by value, the lengths returned or by reference) made the compiler commute or reorder the
+// instructions of that test in eight kernels; this one leaves their code as it was.
+#define FS_LENGTHS(p, b, tx, ty)            \
+    int tx = (p).t_xs[b], ty = (p).t_ys[b]; \
+    tx = tx > (p).Tx ? (p).Tx : tx;         \
+    ty = ty > (p).Ty ? (p).Ty : ty
 
 __device__ __forceinline__ float fs_wave_max(float v) {
 #pragma unroll
@@ -159,8 +165,7 @@ __device__ __forceinline__ float fs_from_lane_above(float edge, float src) {
 // carry an offset beyond the block: the hardware drops the store.
 constexpr unsigned FS_DROP = 0xFFFFFF00u;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t fs_rsrc(const void *base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (unsigned)(bytes < 0xFFFFFF00ull ? bytes : 0xFFFFFF00ull),
-                                             0x00020000);
+    return utterance_rsrc(base, (unsigned)(bytes < 0xFFFFFF00ull ? bytes : 0xFFFFFF00ull));
 }
 __device__ __forceinline__ float fs_bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
@@ -280,12 +285,12 @@ __device__ __forceinline__ void fs_stager_by_hand(const float *in_g, float *out_
         if (st) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); c2 = __builtin_amdgcn_s_memtime(); }
         issue(k + D, s);                                                       // (behind the stores: the wait's count)
         const unsigned long long c3 = st ? __builtin_amdgcn_s_memtime() : 0;
-        fs_lds_barrier();
+        lds_barrier();
         if (st) { sa[0] += c1 - c0; sa[1] += c2 - c1; sa[2] += c3 - c2; sa[3] += __builtin_amdgcn_s_memtime() - c3; }
     };
 #pragma unroll
     for (int d = 0; d < D; ++d) issue(d, q[d]);
-    for (int ph = 0; ph < lag; ++ph) fs_lds_barrier();                         // (this stager's first tile is due in phase `lag`)
+    for (int ph = 0; ph < lag; ++ph) lds_barrier();                            // (this stager's first tile is due in phase `lag`)
     for (int ph = lag; ph < nph; ph += D) {
 #pragma unroll
         for (int d = 0; d < D; ++d)
@@ -404,11 +409,11 @@ __device__ __forceinline__ void fs_grad_stager_by_hand(const float *lp_g, const 
             }
         }
         issue(k + D, sl, sa, o);                              // (behind the stores: the wait's count)
-        fs_lds_barrier();
+        lds_barrier();
     };
 #pragma unroll
     for (int d = 0; d < D; ++d) issue(d, ql[d], qa[d], qo[d]);
-    for (int ph = 0; ph < lag; ++ph) fs_lds_barrier();        // (this stager's first tile is due in phase `lag`)
+    for (int ph = 0; ph < lag; ++ph) lds_barrier();           // (this stager's first tile is due in phase `lag`)
     for (int ph = lag; ph < nph; ph += D) {
 #pragma unroll
         for (int d = 0; d < D; ++d)
@@ -431,9 +436,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_forward_kernel(FwdSumParams
     double *toff = reinterpret_cast<double *>(tout + 2 * TW * ROWS);   // [2][TW]
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     if (!(tx >= 1 && tx <= ty)) {                 // no monotonic alignment exists: loss = +inf
         if (tid == 0) { p.loss[b] = -FS_NEG_INF; p.logz[b] = (double)FS_NEG_INF; }
@@ -538,7 +541,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_forward_kernel(FwdSumParams
                 }
             }
         }
-        fs_lds_barrier();
+        lds_barrier();
     }
 }
 
@@ -553,9 +556,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_backward_kernel(FwdSumParam
     double *toff = reinterpret_cast<double *>(tgr + 2 * TW * ROWS);    // [2][TW] C_y
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const double logz = p.logz[b];                // (-inf: no alignment, by the lengths or by the log-probs)
     const bool ok = tx >= 1 && tx <= ty && fs_has_alignment(logz);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
@@ -660,7 +661,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_backward_kernel(FwdSumParam
                 }
             }
         }
-        fs_lds_barrier();
+        lds_barrier();
     }
 }
 
@@ -704,9 +705,7 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1);
     const bool sweeper = wave < SY_NW;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     double *offs = p.offs + ((size_t)b * SY_NW_MAX + w) * p.NT;
     if (!(tx >= 1 && tx <= ty)) {                             // no monotonic alignment exists: loss = +inf
@@ -790,12 +789,12 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
                 }
                 if (lane < SY_TW && y0 + lane < ty) offs[y0 + lane] = toff[(w * 2 + (ts & 1)) * SY_TW + lane];
             }
-            fs_lds_barrier();
+            lds_barrier();
         };
         stage_issue(0, vA);
         stage_issue(1, vB);
         const int nph = ntl + SY_NW + 1;
-        for (int ph = 0; ph < w; ++ph) fs_lds_barrier();          // (this stager's first tile is due in phase w)
+        for (int ph = 0; ph < w; ++ph) lds_barrier();             // (this stager's first tile is due in phase w)
         for (int ph = w; ph < nph; ph += 2) {
             phase(ph, vA);
             if (ph + 1 < nph) phase(ph + 1, vB);
@@ -879,7 +878,7 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
                 if (p.stamps) { asm volatile("" :: "v"(prev)); c2 = __builtin_amdgcn_s_memtime(); }
                 if (p.stamps) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); c3 = __builtin_amdgcn_s_memtime(); }
             }
-            fs_lds_barrier();
+            lds_barrier();
             if (p.stamps) { sa[0] += c1 - c0; sa[1] += c2 - c1; sa[2] += c3 - c2; sa[3] += __builtin_amdgcn_s_memtime() - c3; }
         }
         if (p.stamps && lane == 0) {
@@ -917,9 +916,7 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1), wr = SY_NW - 1 - w;     // wave SY_NW-1 (the last rows) leads
     const bool sweeper = wave < SY_NW;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     // (log Z = -inf: no alignment, by the lengths or by the log-probs.  BETA_ONLY runs beside the forward sweep and cannot
     // know: it sweeps, and fwdsum_combine_kernel writes the zeros)
     const double logz = BETA_ONLY ? 0.0 : p.logz[b];
@@ -1029,12 +1026,12 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
                 }
                 if (BETA_ONLY && lane < SY_TW && y0 + lane < ty) doffs[y0 + lane] = tdof[(w * 2 + (ks & 1)) * SY_TW + lane];
             }
-            fs_lds_barrier();
+            lds_barrier();
         };
         stage_issue(0, sA);
         stage_issue(1, sB);
         const int nph = ntl + SY_NW + 1;
-        for (int ph = 0; ph < wr; ++ph) fs_lds_barrier();         // (this stager's first tile is due in phase wr)
+        for (int ph = 0; ph < wr; ++ph) lds_barrier();            // (this stager's first tile is due in phase wr)
         for (int ph = wr; ph < nph; ph += 2) {
             phase(ph, sA);
             if (ph + 1 < nph) phase(ph + 1, sB);
@@ -1144,7 +1141,7 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
                 if (kt != 0) frames(std::false_type{});
                 else         frames(std::true_type{});
             }
-            fs_lds_barrier();
+            lds_barrier();
         }
     }
 }
@@ -1177,9 +1174,7 @@ __device__ __forceinline__ void fwdsum_combine_body(const FwdSumParams &p, const
     __shared__ float st[256], ny[256];
     const int b = blockIdx.z, w = blockIdx.y, tid = threadIdx.x;
     const int yb = blockIdx.x * 256;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const bool ok = tx >= 1 && tx <= ty && fs_has_alignment(p.logz[b]);
     {
         const int y = yb + tid;
@@ -1295,9 +1290,7 @@ struct CtcParams {
 __device__ __forceinline__ void ctc_colnorm_body(const CtcParams &q, float (*sm)[64], float (*ss)[64], const int bx, const int b) {
     const FwdSumParams &p = q.f;
     const int fx = threadIdx.x & 63, g = threadIdx.x >> 6, y = bx * 64 + fx;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     float m = FS_NEG, s = 0.f;
     if (y < ty) {
         const float *col = p.logp + (size_t)b * p.Tx * p.Ty + y;
@@ -1348,9 +1341,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_forward_kernel(CtcParam
     float *tnrm = reinterpret_cast<float *>(toff + 2 * TW);            // [2][TW] n_y
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     if (!(tx >= 1 && tx <= ty)) {                 // fewer frames than tokens: no labelling exists, loss = +inf
         if (tid == 0) { p.loss[b] = -FS_NEG_INF; p.logz[b] = (double)FS_NEG_INF; }
@@ -1453,7 +1444,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_forward_kernel(CtcParam
                 }
             }
         }
-        fs_lds_barrier();
+        lds_barrier();
     }
 }
 
@@ -1469,9 +1460,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_backward_kernel(CtcPara
     float *tnrm = reinterpret_cast<float *>(toff + 2 * TW);            // [2][TW] n_y
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const bool ok = tx >= 1 && tx <= ty;
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     const int ntl = ok ? (ty + TW - 1) / TW : 0;
@@ -1586,7 +1575,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_backward_kernel(CtcPara
                 }
             }
         }
-        fs_lds_barrier();
+        lds_barrier();
     }
 }
 
@@ -1616,9 +1605,7 @@ __device__ __forceinline__ void fwdsum_ctc_forward_sys_body(const CtcParams &q, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1);
     const bool sweeper = wave < SY_NW;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     double *offs = p.offs + ((size_t)b * SY_NW_MAX + w) * p.NT;
     if (!(tx >= 1 && tx <= ty)) {                             // fewer frames than tokens: no labelling exists, loss = +inf
@@ -1679,7 +1666,7 @@ __device__ __forceinline__ void fwdsum_ctc_forward_sys_body(const CtcParams &q, 
                 }
                 if (lane < SY_TW && y0 + lane < ty) offs[y0 + lane] = toff[(w * 2 + (ts & 1)) * SY_TW + lane];
             }
-            fs_lds_barrier();
+            lds_barrier();
         }
         return;
     }
@@ -1756,7 +1743,7 @@ __device__ __forceinline__ void fwdsum_ctc_forward_sys_body(const CtcParams &q, 
                 pB = fmaxf(pB - mx, FS_NEG);
             }
         }
-        fs_lds_barrier();
+        lds_barrier();
     }
 }
 
@@ -1795,9 +1782,7 @@ __device__ __forceinline__ void fwdsum_ctc_backward_sys_body(const CtcParams &q,
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1), wr = SY_NW - 1 - w;     // wave SY_NW-1 (the last rows) leads
     const bool sweeper = wave < SY_NW;
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     const bool ok = tx >= 1 && tx <= ty;
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     const int ntl = ok ? (ty + SY_TW - 1) / SY_TW : 0, nph = ntl + SY_NW + 1;
@@ -1869,7 +1854,7 @@ __device__ __forceinline__ void fwdsum_ctc_backward_sys_body(const CtcParams &q,
                 }
                 if (BETA_ONLY && lane < SY_TW && y0 + lane < ty) doffs[y0 + lane] = tdof[(w * 2 + (ks & 1)) * SY_TW + lane];
             }
-            fs_lds_barrier();
+            lds_barrier();
         }
         return;
     }
@@ -1967,7 +1952,7 @@ __device__ __forceinline__ void fwdsum_ctc_backward_sys_body(const CtcParams &q,
                 gB = fmaxf(gB - mx, FS_NEG);
             }
         }
-        fs_lds_barrier();
+        lds_barrier();
     }
 }
 
@@ -1999,9 +1984,7 @@ __global__ __launch_bounds__(2 * SY_NW * 64) void fwdsum_ctc_both_sys_kernel(Ctc
 __device__ __forceinline__ void fwdsum_ctc_finish_loss(const CtcParams &q, const int b) {
     const FwdSumParams &p = q.f;
     __shared__ double part[256];
-    int tx = p.t_xs[b], ty = p.t_ys[b];
-    tx = tx > p.Tx ? p.Tx : tx;
-    ty = ty > p.Ty ? p.Ty : ty;
+    FS_LENGTHS(p, b, tx, ty);
     double ns = 0.0;
     for (int y = threadIdx.x; y < ty; y += 256) ns += (double)q.nrm[(size_t)b * p.Ty + y];
     part[threadIdx.x] = ns;

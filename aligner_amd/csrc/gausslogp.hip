@@ -35,11 +35,9 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 struct GaussParams {
     const float *z;         // [B,C,Ty]
@@ -62,15 +60,6 @@ constexpr int GL_WAVES = 4;
 constexpr int GL_THREADS = GL_WAVES * 64;
 constexpr int GL_ST_AUX = 16;                     // sc1
 constexpr float HALF_LN_2PI = 0.91893853320467274178f;
-
-__device__ __forceinline__ float gl_and_mask(float v, unsigned m) {
-    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & m);
-}
-
-__device__ __forceinline__ void gl_split(float v, __bf16 &hi, __bf16 &lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
-}
 
 // One workgroup per (row tile, utterance).  Lane (row i = 32 r + lane&31, channel half lane>>5) of k-step s holds channels
 // 16 s + 8 (lane>>5) + jj: A[i][k] of v_mfma_f32_32x32x16_bf16.
@@ -100,14 +89,14 @@ __global__ __launch_bounds__(256) void gauss_prep_kernel(GaussParams p) {
         for (int jj = 0; jj < 8; ++jj) {
             const unsigned ok = (i < p.Tx && c0 + jj < p.C) ? ~0u : 0u;      // padding: w = m w = 0, nothing added to k
             const float m = mv[jj], sd = sv[jj];
-            const float w = gl_and_mask(expf(-2.0f * sd), ok);
-            const float mw = gl_and_mask(m * w, ok);
-            acc += gl_and_mask((-HALF_LN_2PI - sd) - 0.5f * (m * mw), ok);
+            const float w = and_mask(expf(-2.0f * sd), ok);
+            const float mw = and_mask(m * w, ok);
+            acc += and_mask((-HALF_LN_2PI - sd) - 0.5f * (m * mw), ok);
             __bf16 h, l;
-            gl_split(w, h, l);
+            split_bf16(w, h, l);
             wh[jj] = h;
             wl[jj] = l;
-            gl_split(mw, h, l);
+            split_bf16(mw, h, l);
             mh[jj] = h;
             ml[jj] = l;
         }
@@ -136,25 +125,10 @@ __global__ __launch_bounds__(GL_THREADS) void gauss_logp_kernel(GaussParams p) {
     const int half = lane >> 5, l31 = lane & 31;
     const int KSc = p.KSc, KS = 2 * KSc;
     int b, fq;
-    if ((p.B & 7) == 0) {                         // the workgroups of one utterance on one XCD: its A fragments stay in that L2
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        fq = slot % p.NQ;
-        b = (slot / p.NQ) * 8 + xcd;
-    } else {
-        b = blockIdx.x / p.NQ;
-        fq = blockIdx.x % p.NQ;
-    }
+    xcd_block_map(p.B, p.NQ, blockIdx.x, b, fq);  // the workgroups of one utterance on one XCD: its A fragments stay in that L2
     const int f0 = 32 * GL_STRIPS * fq;
-    int tx = p.Tx, ty = p.Ty;
-    if (p.t_xs) {
-        tx = p.t_xs[b];
-        tx = tx < 0 ? 0 : (tx > p.Tx ? p.Tx : tx);
-    }
-    if (p.t_ys) {
-        ty = p.t_ys[b];
-        ty = ty < 0 ? 0 : (ty > p.Ty ? p.Ty : ty);
-    }
-    if (tx <= 0 || ty <= 0) tx = ty = 0;
+    int tx, ty;
+    utterance_lengths(p.t_xs, p.t_ys, b, p.Tx, p.Ty, tx, ty);
     const bool live = f0 < ty;                    // (workgroup-uniform) any cell of this frame block inside the lengths
 
     if (live) {
@@ -172,16 +146,16 @@ __global__ __launch_bounds__(GL_THREADS) void gauss_logp_kernel(GaussParams p) {
             for (int jj = 0; jj < 8; ++jj) {
                 const int c = c0 + jj;
                 const float x = Zb[(size_t)(c < p.C ? c : p.C - 1) * p.Ty + colc];
-                v[jj] = gl_and_mask(x, (c < p.C && col < p.Ty) ? ~0u : 0u);
+                v[jj] = and_mask(x, (c < p.C && col < p.Ty) ? ~0u : 0u);
             }
             bf16x8 qh, ql, zh, zl;
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) {
                 __bf16 h, l;
-                gl_split(-0.5f * (v[jj] * v[jj]), h, l);
+                split_bf16(-0.5f * (v[jj] * v[jj]), h, l);
                 qh[jj] = h;
                 ql[jj] = l;
-                gl_split(v[jj], h, l);
+                split_bf16(v[jj], h, l);
                 zh[jj] = h;
                 zl[jj] = l;
             }
@@ -196,8 +170,8 @@ __global__ __launch_bounds__(GL_THREADS) void gauss_logp_kernel(GaussParams p) {
 
     // the utterance's [Tx, ld] block as a buffer resource; a lane whose cell does not exist carries an offset beyond it
     constexpr unsigned esz = OUT16 ? 2u : 4u;
-    const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(
-        static_cast<unsigned char *>(p.out) + (size_t)b * p.Tx * p.ld * esz, 0, (unsigned)p.Tx * (unsigned)p.ld * esz, 0x00020000);
+    const __amdgpu_buffer_rsrc_t out_rs =
+        utterance_rsrc(static_cast<unsigned char *>(p.out) + (size_t)b * p.Tx * p.ld * esz, (unsigned)p.Tx * (unsigned)p.ld * esz);
 
     for (int pr = wave; 2 * pr < p.RTP; pr += GL_WAVES) {
         f32x16 acc[2][GL_STRIPS];

@@ -33,11 +33,9 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int GB_MAX_NCT = 3;                     // channel tiles per wave: 6 accumulator tiles
 constexpr int GB_TARGET_WAVES = 1536;             // the row kernel splits the frame sweep until it has about this many waves
@@ -100,48 +98,12 @@ struct GbParams {
     int B, C, Tx, Ty, ld;
 };
 
-__device__ __forceinline__ float gb_and_mask(float v, unsigned m) {
-    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & m);
-}
-
-__device__ __forceinline__ void gb_split(float v, __bf16 &hi, __bf16 &lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
-}
-
-// the forward's clamping: lengths into [0, extent], an utterance with either length 0 is empty
-__device__ __forceinline__ void gb_lengths(const GbParams &p, int b, int &tx, int &ty) {
-    tx = p.Tx;
-    ty = p.Ty;
-    if (p.t_xs) {
-        tx = p.t_xs[b];
-        tx = tx < 0 ? 0 : (tx > p.Tx ? p.Tx : tx);
-    }
-    if (p.t_ys) {
-        ty = p.t_ys[b];
-        ty = ty < 0 ? 0 : (ty > p.Ty ? p.Ty : ty);
-    }
-    if (tx <= 0 || ty <= 0) tx = ty = 0;
-}
-
-// the forward's two block maps: with B a multiple of 8 the waves of one utterance share an XCD (its fragments stay in that L2)
-__device__ __forceinline__ void gb_block_map(int B, int per_b, unsigned bid, int &b, int &inner) {
-    if ((B & 7) == 0) {
-        const unsigned xcd = bid & 7, slot = bid >> 3;
-        inner = (int)(slot % (unsigned)per_b);
-        b = (int)(slot / (unsigned)per_b) * 8 + (int)xcd;
-    } else {
-        b = (int)(bid / (unsigned)per_b);
-        inner = (int)(bid % (unsigned)per_b);
-    }
-}
-
 // Lane (channel 32 ct + lane&31, half lane>>5) of k-step ks holds tokens 16 ks + 8 half + jj: A[c][k] of the MFMA.
 __global__ __launch_bounds__(64) void gb_prep_col_kernel(GbParams p) {
     const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
     const int ks = blockIdx.x, ct = blockIdx.y, b = blockIdx.z;
     int tx, ty;
-    gb_lengths(p, b, tx, ty);
+    utterance_lengths(p.t_xs, p.t_ys, b, p.Tx, p.Ty, tx, ty);
     const int c = 32 * ct + l31, cc = c < p.C ? c : p.C - 1;
     const float *Mb = p.mean + ((size_t)b * p.C + cc) * p.Tx;
     const float *Sb = p.logstd + ((size_t)b * p.C + cc) * p.Tx;
@@ -157,13 +119,13 @@ __global__ __launch_bounds__(64) void gb_prep_col_kernel(GbParams p) {
     for (int jj = 0; jj < 8; ++jj) {
         const int i = 16 * ks + 8 * half + jj;
         const unsigned ok = (c < p.C && i < tx) ? ~0u : 0u;
-        const float w = gb_and_mask(expf(-2.0f * sv[jj]), ok);
-        const float mw = gb_and_mask(mv[jj] * w, ok);
+        const float w = and_mask(expf(-2.0f * sv[jj]), ok);
+        const float mw = and_mask(mv[jj] * w, ok);
         __bf16 h, l;
-        gb_split(w, h, l);
+        split_bf16(w, h, l);
         wh[jj] = h;
         wl[jj] = l;
-        gb_split(mw, h, l);
+        split_bf16(mw, h, l);
         mh[jj] = h;
         ml[jj] = l;
     }
@@ -179,7 +141,7 @@ __global__ __launch_bounds__(128) void gb_prep_row_kernel(GbParams p) {
     const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5, u = threadIdx.x >> 6;
     const int ch = blockIdx.x, ct = blockIdx.y, b = blockIdx.z;
     int tx, ty;
-    gb_lengths(p, b, tx, ty);
+    utterance_lengths(p.t_xs, p.t_ys, b, p.Tx, p.Ty, tx, ty);
     const int c = 32 * ct + l31, cc = c < p.C ? c : p.C - 1;
     const float *Zb = p.z + ((size_t)b * p.C + cc) * p.Ty;
     float v[8];
@@ -192,12 +154,12 @@ __global__ __launch_bounds__(128) void gb_prep_row_kernel(GbParams p) {
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
         const int j = 32 * ch + 16 * half + 8 * u + jj;
-        const float x = gb_and_mask(v[jj], (c < p.C && j < ty) ? ~0u : 0u);
+        const float x = and_mask(v[jj], (c < p.C && j < ty) ? ~0u : 0u);
         __bf16 h, l;
-        gb_split(x, h, l);
+        split_bf16(x, h, l);
         zh[jj] = h;
         zl[jj] = l;
-        gb_split(x * x, h, l);
+        split_bf16(x * x, h, l);
         qh[jj] = h;
         ql[jj] = l;
     }
@@ -232,10 +194,10 @@ template <int NCT>
 __global__ __launch_bounds__(64, 2) void gb_col_kernel(GbParams p) {
     const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
     int b, inner;
-    gb_block_map(p.B, p.NS * p.NG, blockIdx.x, b, inner);
+    xcd_block_map(p.B, p.NS * p.NG, blockIdx.x, b, inner);
     const int st = inner % p.NS, cg = inner / p.NS;
     int tx, ty;
-    gb_lengths(p, b, tx, ty);
+    utterance_lengths(p.t_xs, p.t_ys, b, p.Tx, p.Ty, tx, ty);
     const int j0 = 32 * st;
     const int col = j0 + l31, colc = col < p.Ty ? col : p.Ty - 1;      // (j0 < Ty: the strip exists)
 
@@ -272,9 +234,9 @@ __global__ __launch_bounds__(64, 2) void gb_col_kernel(GbParams p) {
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) {
                 const int i = 16 * ks + 8 * half + jj;
-                const float v = gb_and_mask(g[jj], i < tx ? colok : 0u) * sc;
+                const float v = and_mask(g[jj], i < tx ? colok : 0u) * sc;
                 __bf16 h, l;
-                gb_split(v, h, l);
+                split_bf16(v, h, l);
                 bh[jj] = h;
                 bl[jj] = l;
             }
@@ -307,10 +269,10 @@ template <int NCT>
 __global__ __launch_bounds__(64, 2) void gb_row_kernel(GbParams p) {
     const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
     int b, inner;
-    gb_block_map(p.B, p.RT * p.nsplit * p.NG, blockIdx.x, b, inner);
+    xcd_block_map(p.B, p.RT * p.nsplit * p.NG, blockIdx.x, b, inner);
     const int rt = inner % p.RT, sp = (inner / p.RT) % p.nsplit, cg = inner / (p.RT * p.nsplit);
     int tx, ty;
-    gb_lengths(p, b, tx, ty);
+    utterance_lengths(p.t_xs, p.t_ys, b, p.Tx, p.Ty, tx, ty);
     if (32 * rt >= tx) return;                    // (wave-uniform) gb_finish_kernel never reads a tile past t_x
     const int i = 32 * rt + l31, ic = i < p.Tx ? i : p.Tx - 1;
     const int ch0 = sp * p.per;
@@ -363,10 +325,10 @@ __global__ __launch_bounds__(64, 2) void gb_row_kernel(GbParams p) {
 #pragma unroll
                 for (int jj = 0; jj < 8; ++jj) {
                     const int j = 32 * ch + 16 * half + 8 * u + jj;
-                    const float v = gb_and_mask(g[8 * u + jj], j < ty ? rowok : 0u) * sc;
+                    const float v = and_mask(g[8 * u + jj], j < ty ? rowok : 0u) * sc;
                     r += v;
                     __bf16 h, l;
-                    gb_split(v, h, l);
+                    split_bf16(v, h, l);
                     bh[jj] = h;
                     bl[jj] = l;
                 }
@@ -403,7 +365,7 @@ __global__ __launch_bounds__(256) void gb_finish_kernel(GbParams p) {
     const int i = 32 * rt + l31, c = 8 * blockIdx.y + (threadIdx.x >> 5);
     if (c >= p.C || i >= p.Tx) return;
     int tx, ty;
-    gb_lengths(p, b, tx, ty);
+    utterance_lengths(p.t_xs, p.t_ys, b, p.Tx, p.Ty, tx, ty);
     float dm = 0.f, ds = 0.f;
     if (i < tx) {
         float R = 0.f, P = 0.f, Q = 0.f;

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(GN_THREADS) void gauss_nll_kernel(const float *__re
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *acc = reinterpret_cast<float *>(wave_tot + GN_WAVES) + (size_t)wave * CW * 2 * Tx;
     scan_durations(dur + (size_t)b * Tx, ends, wave_tot, Tx);
-    const int ty = clamp_t_y(t_ys, b, Ty);
+    const int ty = clamp_len(t_ys, b, Ty);
     float sc = 1.f;
     if constexpr (GRAD) {
         if (scale) sc = scale[b];
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64) void gauss_nll_finish_kernel(const float *__res
         n += __shfl_down(n, o);
     }
     if (lane == 0) {
-        const int ty = clamp_t_y(t_ys, b, Ty);
+        const int ty = clamp_len(t_ys, b, Ty);
         if (nll) nll[b] = s;
         if (count) count[b] = n < ty ? (int)n : ty;
     }

@@ -43,6 +43,7 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
 
@@ -55,12 +56,6 @@ constexpr int GU_JC = 32;                    // contracted indices per chunk
 constexpr int GU_SRC_LD = GU_CS + 4;         // LDS row pitch of the transposed source chunk (16-byte rows stay aligned)
 constexpr int GU_H_LD = GU_JC + 4;           // ... of the frames kernel's [channel][token] chunk
 constexpr int GU_MAX_TX = 2048;
-
-__device__ inline int gu_clamp_len(const int *__restrict__ t, int b, int T) {
-    int v = t ? t[b] : T;
-    v = v < T ? v : T;
-    return v > 0 ? v : 0;
-}
 
 // the one statement of the energy: every kernel, and the tests' restatement, round it this way
 __device__ inline float gu_energy(float tau, float c, float a, float g) {
@@ -90,7 +85,7 @@ __global__ __launch_bounds__(GU_THREADS) void gauss_up_band_kernel(const float *
     __shared__ float s_amin[GU_WAVES], s_gmax[GU_WAVES];
     __shared__ int s_bad[GU_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
-    const int tx = gu_clamp_len(t_xs, b, Tx), ty = gu_clamp_len(t_ys, b, Ty);
+    const int tx = clamp_len(t_xs, b, Tx), ty = clamp_len(t_ys, b, Ty);
     const float *cb = cen + (size_t)b * Tx, *ab = prec + (size_t)b * Tx;
     const float *gb = lw ? lw + (size_t)b * Tx : nullptr;
     float amin = INFINITY, gmax = -INFINITY;
@@ -205,7 +200,7 @@ __global__ __launch_bounds__(GU_THREADS) void gauss_up_mix_kernel(const float *_
     __shared__ int s_rng[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tile = blockIdx.x, c0 = blockIdx.y * GU_CS, b = blockIdx.z;
-    const int tx = gu_clamp_len(t_xs, b, Tx), ty = gu_clamp_len(t_ys, b, Ty);
+    const int tx = clamp_len(t_xs, b, Tx), ty = clamp_len(t_ys, b, Ty);
     const int I = TOK ? Tx : Ty, J = TOK ? Ty : Tx;
     const int i = tile * GU_TILE + lane;
     const bool valid = i < (TOK ? tx : ty);
@@ -330,7 +325,7 @@ __global__ __launch_bounds__(GU_THREADS) void gauss_up_frames_kernel(const float
     __shared__ double s_den[GU_WAVES * 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tile = blockIdx.x, b = blockIdx.y;
-    const int ty = gu_clamp_len(t_ys, b, Ty);
+    const int ty = clamp_len(t_ys, b, Ty);
     const int y = tile * GU_TILE + lane;
     const bool valid = y < ty;
     const float tau = (float)y + off;
@@ -436,7 +431,7 @@ __global__ __launch_bounds__(GU_THREADS) void gauss_up_finish_kernel(const float
                                                                      float *__restrict__ dlw, int Tx, int ntiles) {
     const int b = blockIdx.y, x = blockIdx.x * GU_THREADS + threadIdx.x;
     if (x >= Tx) return;
-    const int tx = gu_clamp_len(t_xs, b, Tx);
+    const int tx = clamp_len(t_xs, b, Tx);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
     if (x < tx) {
         for (int t = 0; t < ntiles; ++t) {

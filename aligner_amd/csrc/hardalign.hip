@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void bin_loss_kernel(const void *__restrict__ 
     __shared__ float wsum[4];
     __shared__ int wcnt[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int ty = clamp_t_y(t_ys, b, Ty);
+    const int ty = clamp_len(t_ys, b, Ty);
     float s = 0.f;
     int n = 0;
     for (int y = tid; y < Ty; y += 256) {
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void bin_grad_scatter_kernel(const void *__res
                                                                float *__restrict__ grad, int Tx, int Ty) {
     const int b = blockIdx.y, y = blockIdx.x * 256 + threadIdx.x;
     if (y >= Ty) return;
-    const int ty = clamp_t_y(t_ys, b, Ty);
+    const int ty = clamp_len(t_ys, b, Ty);
     int x;
     float lp;
     if (path_cell(logp, dtype, ld, tok, b, y, Tx, Ty, ty, &x, &lp) && lp > min_logp)
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void bin_grad_write_kernel(const void *__restr
     if (y0 >= Ty) return;
     const int xpz = (Tx + gridDim.z - 1) / gridDim.z;
     const int x0 = blockIdx.z * xpz, x1 = (x0 + xpz < Tx) ? x0 + xpz : Tx;
-    const int ty = clamp_t_y(t_ys, b, Ty);
+    const int ty = clamp_len(t_ys, b, Ty);
     const float g = -scale[b];
     int hot[VEC];                                             // the row that gets g in this column, -1: none here
 #pragma unroll

@@ -44,6 +44,7 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 #include "maxpath_sweep_asm.inc"
 #include "maxpath_walk_asm.inc"
 
@@ -698,13 +699,10 @@ __device__ __forceinline__ void scan4(float &nf, const float4 &v) {
         : "+v"(nf) : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
 }
 
-// Buffer resource over one utterance's [Tx,Ty] fp32 block: loads take a per-lane byte offset that never
-// changes (row and column group) plus a scalar tile offset, so a tile costs the loader no address
+// Loads through the buffer resource over one utterance's [Tx,Ty] fp32 block (utterance_rsrc) take a per-lane byte
+// offset that never changes (row and column group) plus a scalar tile offset, so a tile costs the loader no address
 // arithmetic; reads past the block (last rows, last partial tile) return 0 instead of faulting.
 typedef unsigned __attribute__((ext_vector_type(4))) u32x4r;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t utterance_rsrc(const void *base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
-}
 __device__ __forceinline__ float4 buffer_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     // (cast the whole vector: hipcc 7.2 turns per-component reads of the builtin's result into a
     // one-dword load splatted over the four components)

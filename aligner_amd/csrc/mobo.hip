@@ -36,6 +36,7 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
 
@@ -177,10 +178,6 @@ __device__ __forceinline__ void mb_active_rows(int I, int J, int D, int a, int b
         i1 = hi_i;
     }
 }
-
-// Barrier for LDS hand-offs only: __syncthreads() also drains vmcnt, which would put the latency of the next
-// row's loads and of this row's result stores on every row.
-__device__ __forceinline__ void mb_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- cross-lane helpers of the split form -------------------------------------------------------------------
 __device__ __forceinline__ int mb_quad_xor_i(int v, int m) {       // the value of lane (lane ^ m), m = 1 or 2
@@ -547,7 +544,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_kernel(MoboParams p) {
                     g.sV[bo + h] = bad ? MB_NEG : __builtin_bit_cast(float, w2);
                 }
             }
-            mb_lds_barrier();
+            lds_barrier();
             // ---- phase 2: the windows [j-D, j) ----
 #pragma unroll 1
             for (int j = j1; j < bnd; j += T) {
@@ -703,7 +700,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
         sV[h] = MB_NEG;    sV[W + h] = MB_NEG;
         sT[h] = 0.f;       sT[W + h] = 0.f;
     }
-    mb_lds_barrier();
+    lds_barrier();
     const int pi = tid / H, sub = tid - pi * H;    // H consecutive lanes per position
     const int j1 = a + pi;
     const bool mine = !helper && j1 < bnd;
@@ -814,7 +811,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
                     const bool wfit = __builtin_amdgcn_ballot_w64(!fits) == 0;
                     mb_report_put(sRep, i & 1, wave, wm, wfit ? 0 : 1);
                 }
-                mb_lds_barrier();
+                lds_barrier();
                 int Rn, slow_;
                 mb_report_get(sRep, i & 1, lane, Rn, slow_);
                 R = (Rn != MB_DEADM) ? Rn : R;
@@ -905,7 +902,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
         }
         MB_STAMP(1)
         MB_STAMP(2)
-        mb_lds_barrier();
+        lds_barrier();
         MB_STAMP(3)
         // ---- phase 2: the windows [j-D, j) ----
         {
@@ -1048,7 +1045,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_map_kernel(MoboParams p) {
         sV[h] = MB_NEG;
         sV[W + h] = MB_NEG;
     }
-    mb_lds_barrier();
+    lds_barrier();
     const int pi = tid / H, sub = tid - pi * H;
     const int j1 = a + pi;
     const bool mine = !helper && j1 < bnd;
@@ -1116,7 +1113,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_map_kernel(MoboParams p) {
 #pragma unroll 1
                     for (int h = hl + 64; h < D; h += 64) halo_entry(h, MB_FILL);
                 }
-                mb_lds_barrier();
+                lds_barrier();
             }
         }
         if (gave_up) {
@@ -1156,7 +1153,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_map_kernel(MoboParams p) {
             *(mine ? sV + bo + D + pi : sSpare) = v;
             mb_ring_store(publishes ? ring_out + (size_t)i * 3 * D + (j1 - (bnd - D)) : trash, __builtin_bit_cast(unsigned, v));
         }
-        mb_lds_barrier();
+        lds_barrier();
         {   // phase 2: the window [j-D, j): its largest v, among equals the largest index
             const float ev = mb_value<VT>(e_c) * MB_LOG2E;
             const bool feasible = mine && j1 >= lo && j1 <= hi;
@@ -1294,7 +1291,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_sum_kernel(MoboParams p) {
         sS[h] = 0.f;       sS[W + h] = 0.f;
         sT[h] = 0.f;       sT[W + h] = 0.f;
     }
-    mb_lds_barrier();
+    lds_barrier();
     const int pi = tid / H, sub = tid - pi * H;
     const int j1 = a + pi;
     const bool mine = !helper && j1 < bnd;
@@ -1388,7 +1385,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_sum_kernel(MoboParams p) {
                     const bool wfit = __builtin_amdgcn_ballot_w64(!fits) == 0;
                     mb_report_put(sRep, i & 1, wave, wm, wfit ? 0 : 1);
                 }
-                mb_lds_barrier();
+                lds_barrier();
                 int Rn, slow_;
                 mb_report_get(sRep, i & 1, lane, Rn, slow_);
                 R = (Rn != MB_DEADM) ? Rn : R;
@@ -1448,7 +1445,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_sum_kernel(MoboParams p) {
             mb_ring_store(r, __builtin_bit_cast(unsigned, (float)M));
             mb_ring_store(r + (publishes ? D : 0), __builtin_bit_cast(unsigned, sm));
         }
-        mb_lds_barrier();
+        lds_barrier();
         {   // phase 2: the window [j-D, j)
             int Rn, slow;
             mb_report_get(sRep, i & 1, lane, Rn, slow);

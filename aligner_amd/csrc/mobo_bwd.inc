@@ -231,7 +231,7 @@ __global__ __launch_bounds__(1024) void mobo_bwd_chain_kernel(MoboBwdParams p) {
                 sQ[bo + nloc + h] = bad ? MB_NEG : __builtin_bit_cast(float, w1);
             }
         }
-        mb_lds_barrier();
+        lds_barrier();
         // ---- phase 2: Y_i(k) = sum_{j in (k, k+D]} Z_i(j) 2^(u_i(k) + q_i(j)) ----
 #pragma unroll 1
         for (int x = tid; x < nloc; x += T) {
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(1024) void mobo_bwd_chain_one_kernel(MoboBwdParams 
         sQ[nloc + h] = MB_NEG;    sQ[W + nloc + h] = MB_NEG;
         sT[nloc + h] = 0.f;       sT[W + nloc + h] = 0.f;
     }
-    mb_lds_barrier();
+    lds_barrier();
     const int pi = tid / H, sub = tid - pi * H;
     const int j1 = a + pi;
     const bool mine = !helper && j1 < bnd;
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(1024) void mobo_bwd_chain_one_kernel(MoboBwdParams 
                     const int wm = lm ? __builtin_amdgcn_readlane(Mstat, __builtin_ctzll(lm)) : MB_DEADM;
                     mb_report_put(sRep, i & 1, wave, wm, wfit ? 0 : 1);
                 }
-                mb_lds_barrier();
+                lds_barrier();
                 int Rn, slow;
                 mb_report_get(sRep, i & 1, lane, Rn, slow);
                 R = (Rn != MB_DEADM) ? Rn : R;
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(1024) void mobo_bwd_chain_one_kernel(MoboBwdParams 
         MB_STAMP(5)
         unsigned long long bw_t = 0;
         if (STAMPS && p.stamps != nullptr) bw_t = __builtin_amdgcn_s_memtime();           // every wave: its own wait at the barrier
-        mb_lds_barrier();
+        lds_barrier();
         if (STAMPS && p.stamps != nullptr) {
             const unsigned long long t_ = __builtin_amdgcn_s_memtime();
             bw_acc += t_ - bw_t;

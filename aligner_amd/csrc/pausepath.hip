@@ -32,6 +32,7 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
 namespace {
@@ -88,9 +89,6 @@ __device__ __forceinline__ float pp_wave_shr1(float lane0, float src) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lane0), __builtin_bit_cast(int, src),
                                                                  0x138 /* wave_shr:1 */, 0xf, 0xf, false));
 }
-
-// The per-frame barrier orders LDS traffic only: the score loads in flight stay in flight across it.
-__device__ __forceinline__ void pp_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Every element of every requested output of an utterance without a path.
 __device__ __forceinline__ void pp_write_infeasible(const PauseParams &p, int b) {
@@ -211,7 +209,7 @@ __global__ __launch_bounds__(PP_THREADS) void pausepath_kernel(PauseParams p) {
 #pragma unroll
                 for (int r = 0; r < R; ++r) v[r][j % PF] = pp_load<VT>(p.value, rowoff[r] + yn);
                 if (HASP) pv[j % PFP] = pzv[(y + PFP < ty) ? y + PFP : ty - 1];
-                pp_lds_barrier();
+                lds_barrier();                      // (LDS traffic only: the score loads in flight stay in flight across it)
                 __builtin_amdgcn_sched_barrier(0);                   // a frame's instructions stay in their frame (registers)
             }
         }

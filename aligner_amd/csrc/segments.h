@@ -8,6 +8,8 @@
 
 #include <utility>
 
+#include "device.h"
+
 namespace aligner {
 
 constexpr int DUR_SCAN_THREADS = 256;
@@ -48,13 +50,6 @@ __device__ inline int owner_of(const int *ends, int lo, int Tx, int y) {
         if (ends[mid] > y) hi = mid; else lo = mid + 1;
     }
     return lo;
-}
-
-// utterance b's t_y within [0, Ty]; Ty where the caller gave no lengths
-__device__ inline int clamp_t_y(const int *__restrict__ t_ys, int b, int Ty) {
-    int ty = t_ys ? t_ys[b] : Ty;
-    ty = ty < Ty ? ty : Ty;
-    return ty > 0 ? ty : 0;
 }
 
 // Keys of the lane's VEC frames y0 .. y0+VEC-1.  The key of a frame is its token, Tx for a frame that does not count

@@ -34,11 +34,9 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 struct SoftAttnParams {
     const float *keys;      // [B,C,Tx]
@@ -65,12 +63,6 @@ constexpr int SA_THREADS = SA_WAVES * 64;
 constexpr float NEG_INF_F = -__builtin_huge_valf();
 constexpr float LOG2E_F = 1.4426950408889634f, LN2_F = 0.6931471805599453f;
 
-// v or +0.0 without a select on the loaded value (a select fed by a load is turned back into a
-// branch around the load, which serialises the loads)
-__device__ __forceinline__ float and_mask(float v, unsigned m) {
-    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & m);
-}
-
 // Hand-issued loads for the two operand fetches: with compiler-issued loads the scheduler wraps every
 // masked load in "load, s_waitcnt vmcnt(0), select" and the 40 loads of a lane run one after the other.
 // The compiler does not see these loads' vmcnt; consumers go through wait_regs8, which carries the
@@ -88,11 +80,6 @@ __device__ __forceinline__ void wait_regs8(float (&r)[8]) {       // CNT < 0: de
     else
         asm volatile(""
                      : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]));
-}
-
-__device__ __forceinline__ void split_bf16(float v, __bf16 &hi, __bf16 &lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
 }
 
 // one log-prob to logp[idx]: fp32, or bf16 (RNE) when the caller asked for 16-bit log-probs
@@ -334,7 +321,7 @@ __global__ __launch_bounds__(SA_THREADS, (KS == 16 && MULTI) ? 1 : 2) void softa
     const int swv = SA_WAVES / nsp;                               // strips per workgroup
     const int NQ = (p.Ty + 32 * swv - 1) / (32 * swv);
     int b, fq;
-    if ((p.B & 7) == 0) {
+    if ((p.B & 7) == 0) {                             // xcd_block_map (device.h), written out: see there
         const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
         fq = slot % NQ;
         b = (slot / NQ) * 8 + xcd;
@@ -344,11 +331,7 @@ __global__ __launch_bounds__(SA_THREADS, (KS == 16 && MULTI) ? 1 : 2) void softa
     }
     const int col = fq * (32 * swv) + (wave % swv) * 32 + (lane & 31);
     const bool col_ok = col < p.Ty;
-    int tx = p.Tx;
-    if (p.t_xs) {
-        tx = p.t_xs[b];
-        tx = tx < 0 ? 0 : (tx > p.Tx ? p.Tx : tx);
-    }
+    const int tx = clamp_len_lo(p.t_xs, b, p.Tx);
     const float *Qb = p.queries + (size_t)b * p.C * p.Ty;
     const bool l2 = (p.sim == ALIGNER_SIM_L2);
     const float scale = l2 ? -p.temperature : p.temperature;
@@ -569,9 +552,8 @@ __global__ __launch_bounds__(SA_THREADS, (KS == 16 && MULTI) ? 1 : 2) void softa
             // store (a uniform branch costs a wave ~20 cycles, an exec-masked store a save / branch / restore):
             // a uniform row offset (scalar, a compile-time multiple of Ty) plus one 32-bit lane offset.
             const unsigned esz = p.out16 ? 2u : 4u;
-            const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(
-                reinterpret_cast<unsigned char *>(p.logp) + (size_t)b * p.Tx * p.Ty * esz, 0,
-                (unsigned)p.Tx * (unsigned)p.Ty * esz, 0x00020000);
+            const __amdgpu_buffer_rsrc_t out_rs = utterance_rsrc(
+                reinterpret_cast<unsigned char *>(p.logp) + (size_t)b * p.Tx * p.Ty * esz, (unsigned)p.Tx * (unsigned)p.Ty * esz);
             const unsigned lane_byte = col_ok ? (unsigned)(4 * half * p.Ty + col) * esz : 0x80000000u;
             const unsigned row_bytes = (unsigned)p.Ty * esz;
             if (!p.out16) {                                                  // uniform, once
@@ -756,8 +738,6 @@ constexpr int RT_RING = 3;        // split strips in LDS
 // run straddles two lines); the search that reads them next is not slower (32.3 against 32.5 us: Infinity Cache)
 constexpr int RT_ST_AUX = 16;
 
-__device__ __forceinline__ void rt_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // LDS-DMA: 64 lanes x 16 bytes from per-lane global addresses (sbase + voff) to LDS [lds_dst + 16*lane].  The
 // instruction's offset field moves BOTH addresses, so up to four 1 KB pieces share one M0 setting: piece i of a group
 // lands at lds_dst + 1024 i and its base pointer is passed less 1024 i (M0 save / restore and the wait states around
@@ -846,7 +826,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
     const int half = lane >> 5, l31 = lane & 31;
     const int NQ = (p.Ty + 32 * RT_STRIPS - 1) / (32 * RT_STRIPS);
     int b, fq;
-    if ((p.B & 7) == 0) {                             // the workgroups of one utterance on one XCD (see softattn_kernel)
+    if ((p.B & 7) == 0) {                             // xcd_block_map (device.h), written out: see there
         const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
         fq = slot % NQ;
         b = (slot / NQ) * 8 + xcd;
@@ -932,8 +912,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
         // 16k + 8 half + jj), and the loader converts them as they are: plain loads return 1.2 k cycles after the
         // kernel's start, the first LDS-DMA instructions of a wave took 3 k cycles to issue.
         float q0[KS][8], q1[KS][8];
-        const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float *>(Qb), 0, (unsigned)p.C * (unsigned)p.Ty * 4u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t qrs = utterance_rsrc(Qb, (unsigned)p.C * (unsigned)p.Ty * 4u);
         auto load_strip = [&](float (&v)[KS][8], int s) {
             int cf = f0 + 32 * s + l31;
             cf = cf < p.Ty ? cf : p.Ty - 1;
@@ -965,13 +944,13 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
         __builtin_amdgcn_sched_barrier(0);
         load_strip(q1, 1);                            // (behind strip 0's conversion: nothing of it in front of the first strip)
         RT_STAMP(1);
-        rt_barrier();                                 // barrier A: strip 0 is in the ring
+        lds_barrier();                                // barrier A: strip 0 is in the ring
         issued = 2;
         issue_upto(3);                                // strip 2 by LDS-DMA while strip 1's loads land; the others behind barrier B
         RT_STAMP(11);
         to_ring(q1, 1);
         RT_STAMP(14);
-        rt_barrier();                                 // barrier B (= -1): strip 1 is in the ring
+        lds_barrier();                                // barrier B (= -1): strip 1 is in the ring
         for (int j = 0; j < NS; ++j) {
             if (j > 0) merge(j - 1);                  // first: the compute waves' stores of strip j-1 wait for it
             if (lane < 32) c0buf[(j & 1) * 32 + lane] = __builtin_bit_cast(float, RT_PENDING);   // (strip j-2's: read before barrier j-1)
@@ -984,7 +963,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
                 split(j + 2);
             }
             RT_STAMP(8 + 4 * j);
-            rt_barrier();                             // barrier j
+            lds_barrier();                            // barrier j
             RT_STAMP(9 + 4 * j);
         }
         merge(NS - 1);
@@ -993,11 +972,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
     }
 
     // ---------------- compute wave: row tile `tile` ----------------
-    int tx = p.Tx;
-    if (p.t_xs) {
-        tx = p.t_xs[b];
-        tx = tx < 0 ? 0 : (tx > p.Tx ? p.Tx : tx);
-    }
+    const int tx = clamp_len_lo(p.t_xs, b, p.Tx);
     const bool l2 = (p.sim == ALIGNER_SIM_L2);
     const float scale = l2 ? -p.temperature : p.temperature;
     const float s2 = scale * LOG2E_F;                 // logits are kept in base 2
@@ -1012,8 +987,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
     {
         const float *Kb = p.keys + (size_t)b * p.C * p.Tx;
         {
-            const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float *>(Kb), 0, (unsigned)p.C * (unsigned)p.Tx * 4u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t krs = utterance_rsrc(Kb, (unsigned)p.C * (unsigned)p.Tx * 4u);
             const int ic = row_i < p.Tx ? row_i : p.Tx - 1;
             const unsigned voff = 4u * (unsigned)(8 * half * p.Tx + ic);
 #pragma unroll
@@ -1050,7 +1024,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
         for (int gq = 0; gq < 4; ++gq) bz[gq] = *reinterpret_cast<const float4 *>(knl + tile * 32 + 8 * gq + 4 * half);
     }
     RT_STAMP(1);
-    rt_barrier();                                     // barrier A: strip 0 is in the ring
+    lds_barrier();                                    // barrier A: strip 0 is in the ring
 
     bf16x8 bh[KS], bl[KS];
     auto read_b = [&](int s) {
@@ -1069,9 +1043,8 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
     // the utterance's [Tx,Ty] block as a buffer resource: stores to rows >= Tx of the last tile are dropped by the
     // hardware, a lane whose frame does not exist carries an offset beyond any block (softattn_kernel's store path)
     constexpr unsigned esz = OUT16 ? 2u : 4u;
-    const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<unsigned char *>(p.logp) + (size_t)b * p.Tx * p.ldo * esz, 0, (unsigned)p.Tx * (unsigned)p.ldo * esz,
-        0x00020000);
+    const __amdgpu_buffer_rsrc_t out_rs = utterance_rsrc(
+        reinterpret_cast<unsigned char *>(p.logp) + (size_t)b * p.Tx * p.ldo * esz, (unsigned)p.Tx * (unsigned)p.ldo * esz);
     const unsigned row_bytes = (unsigned)p.ldo * esz;
     const unsigned tile_bytes = (unsigned)(32 * tile) * row_bytes;
     auto lane_byte_of = [&](int j) {
@@ -1101,7 +1074,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[k], bh[k], acc, 0, 0, 0);
         }
     }
-    rt_barrier();                                     // barrier B (= -1): strip 1 is in the ring
+    lds_barrier();                                    // barrier B (= -1): strip 1 is in the ring
     RT_STAMP(2);
     // Strip j's iteration (between barriers j-1 and j) carries three strips: the MFMAs of strip j+1, the softmax
     // statistics of strip j (logits from the accumulators of the previous iteration's MFMAs) and the STORES of strip
@@ -1195,7 +1168,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void softattn_rt_kernel(SoftAttnPara
         if (lane < 32) stat[((j & 1) * NT + tile) * 32 + lane] = make_float2(tmax, ls);
         lane_byteP = lane_byte_of(j);
         RT_STAMP(8 + 4 * j);
-        rt_barrier();
+        lds_barrier();
         RT_STAMP(9 + 4 * j);
     };
     // the last strip's stores
@@ -1261,11 +1234,7 @@ __global__ __launch_bounds__(256) void softattn_exact_kernel(SoftAttnParams p, i
     const int b = blockIdx.x / NQ, fq = blockIdx.x % NQ;
     const int col = fq * 128 + wave * 32 + (lane & 31);
     const bool col_ok = col < p.Ty;
-    int tx = p.Tx;
-    if (p.t_xs) {
-        tx = p.t_xs[b];
-        tx = tx < 0 ? 0 : (tx > p.Tx ? p.Tx : tx);
-    }
+    const int tx = clamp_len_lo(p.t_xs, b, p.Tx);
     const bool l2 = (p.sim == ALIGNER_SIM_L2);
     const float scale = l2 ? -p.temperature : p.temperature;
     const float *Kb = p.keys + (size_t)b * p.C * p.Tx;

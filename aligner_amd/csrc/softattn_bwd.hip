@@ -26,10 +26,9 @@
 
 #include "aligner_amd.h"
 #include "common.h"
+#include "device.h"
 
 namespace aligner {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr float SB_NEG_INF = -__builtin_huge_valf();
 constexpr int SB_THREADS = 256;                 // 4 waves
@@ -50,15 +49,6 @@ struct SaBwdParams {
     int l2;
     int GE;                 // column kernel: 32-row tiles staged per group
 };
-
-__device__ __forceinline__ int sb_len(const SaBwdParams &p, int b) {
-    int tx = p.Tx;
-    if (p.t_xs) {
-        tx = p.t_xs[b];
-        tx = tx < 0 ? 0 : (tx > p.Tx ? p.Tx : tx);
-    }
-    return tx;
-}
 
 // the two halves of a wave hold the same frames (rows 4h + ...): combine in a fixed order so both get the same bits
 __device__ __forceinline__ float sb_sum_halves(float v, int half) {
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(SB_THREADS) void softattn_bwd_col_kernel(SaBwdParam
     const int b = blockIdx.x / NJ;
     const int col = (blockIdx.x % NJ) * 128 + wave * 32 + (lane & 31);
     const bool col_ok = col < p.Ty;
-    const int tx = sb_len(p, b);
+    const int tx = clamp_len_lo(p.t_xs, b, p.Tx);
     const float scale = p.l2 ? -p.temperature : p.temperature;
     const float *Kb = p.keys + (size_t)b * p.C * p.Tx;
     const float *Qb = p.queries + (size_t)b * p.C * p.Ty;
@@ -320,7 +310,7 @@ __global__ __launch_bounds__(SB_THREADS) void softattn_bwd_row_kernel(SaBwdParam
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     const int RT = (p.Tx + 31) / 32;
     const int b = blockIdx.x / RT, i0 = 32 * (blockIdx.x % RT);
-    const int tx = sb_len(p, b);
+    const int tx = clamp_len_lo(p.t_xs, b, p.Tx);
     float *dkb = p.dk + (size_t)b * p.C * p.Tx;
     if (i0 >= tx) {                       // a tile of masked rows: dK = 0 exactly
         for (int idx = 32 * 32 * ct0 + tid; idx < cend * 32; idx += SB_THREADS) {

@@ -20,18 +20,12 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._operands import f32c, gaussian_shapes, lengths, one_gpu, per_utterance, ptr, stream
 from .maxpath import Alignment, align
 from .objective import forward_sum
 from .softattn import pitched_logp
 
 _workspaces = _lib.StreamWorkspaces(zero=False)
-
-
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
 
 
 def gaussian_logp(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_x: Optional[torch.Tensor] = None,
@@ -57,17 +51,7 @@ def gaussian_logp(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_x
             raise ValueError("differentiable=True needs out_dtype torch.float32")
         if any(isinstance(t, torch.Tensor) and t.requires_grad for t in (z, mean, logstd)) and torch.is_grad_enabled():
             return _GaussianLogp.apply(z, mean, logstd, t_x, t_y, pitched)
-    for t, name in ((z, "z"), (mean, "mean"), (logstd, "logstd")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3:
-            raise ValueError(f"{name} must be a [B,C,T] tensor")
-    B, C, Ty = z.shape
-    B2, C2, Tx = mean.shape
-    if B2 != B or C2 != C:
-        raise ValueError(f"z {tuple(z.shape)} and mean {tuple(mean.shape)} disagree in B or C")
-    if tuple(logstd.shape) != tuple(mean.shape):
-        raise ValueError(f"logstd {tuple(logstd.shape)} must have mean's shape {tuple(mean.shape)}")
-    if C < 1:
-        raise ValueError("C must be at least 1")
+    B, C, Tx, Ty = gaussian_shapes(z, mean, logstd)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.float32, torch.bfloat16):
@@ -80,22 +64,15 @@ def gaussian_logp(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_x
         if (tuple(out.shape) != (B, Tx, Ty) or (Ty > 1 and out.stride(2) != 1) or ld < Ty or (B > 1 and out.stride(0) != Tx * ld)
                 or (ld != Ty and (ld * out.element_size()) % 16 != 0)):
             raise ValueError("out must be a [B,T_text,T_mel] tensor, contiguous or with a row pitch (pitched_logp())")
-    for t, name in ((z, "z"), (mean, "mean"), (logstd, "logstd")):
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a GPU tensor")
-    dev = z.device
-    if mean.device != dev or logstd.device != dev or (out is not None and out.device != dev):
+    dev = one_gpu(((z, "z"), (mean, "mean"), (logstd, "logstd")), "z, mean, logstd and out")
+    if out is not None and out.device != dev:
         raise ValueError("z, mean, logstd and out must be on the same device")
-    for t, name in ((t_x, "t_x"), (t_y, "t_y")):
-        if t is not None and t.numel() != B:
-            raise ValueError(f"{name} must have one entry per utterance")
+    per_utterance(t_x, B, "t_x")
+    per_utterance(t_y, B, "t_y")
     _lib.require_gpu()
     with torch.no_grad(), torch.cuda.device(dev):
-        zc, mc, sc = _f32(z), _f32(mean), _f32(logstd)
-        if t_x is not None:
-            t_x = t_x.to(device=dev, dtype=torch.int32).contiguous()
-        if t_y is not None:
-            t_y = t_y.to(device=dev, dtype=torch.int32).contiguous()
+        zc, mc, sc = f32c(z), f32c(mean), f32c(logstd)
+        t_x, t_y = lengths(t_x, B, dev, "t_x"), lengths(t_y, B, dev, "t_y")
         if out is None:
             out = pitched_logp(B, Tx, Ty, dev, out_dtype) if pitched else torch.empty((B, Tx, Ty), dtype=out_dtype, device=dev)
             if pitched:
@@ -107,10 +84,9 @@ def gaussian_logp(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, t_x
         nws = lib.aligner_gauss_logp_workspace_bytes(B, C, Tx)
         ws = _workspaces.get(dev, max(nws, 1))
         _lib.check(lib.aligner_gauss_logp(
-            zc.data_ptr(), mc.data_ptr(), sc.data_ptr(), None if t_x is None else t_x.data_ptr(),
-            None if t_y is None else t_y.data_ptr(), out.data_ptr(),
+            zc.data_ptr(), mc.data_ptr(), sc.data_ptr(), ptr(t_x), ptr(t_y), out.data_ptr(),
             _lib.DT_BF16 if out_dtype == torch.bfloat16 else _lib.DT_F32, ld, ws.data_ptr(), ws.numel(),
-            B, C, Tx, Ty, torch.cuda.current_stream(dev).cuda_stream))
+            B, C, Tx, Ty, stream(dev)))
     return out
 
 
@@ -147,39 +123,19 @@ def gaussian_logp_backward(grad_value: torch.Tensor, z: torch.Tensor, mean: torc
     holds there), frames >= t_y and tokens >= t_x get 0.0.  grad_scale [B]: grad_value[b] is read as
     grad_scale[b] * grad_value[b] (forward_sum()'s stored gradient with a per-utterance cotangent, no scaling pass).
     Deterministic (no atomics).  Asynchronous on the current stream."""
-    for t, name in ((z, "z"), (mean, "mean"), (logstd, "logstd"), (grad_value, "grad_value")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3:
-            raise ValueError(f"{name} must be a [B,C,T] tensor" if name != "grad_value"
-                             else "grad_value must be a [B,T_text,T_mel] tensor")
-    B, C, Ty = z.shape
-    B2, C2, Tx = mean.shape
-    if B2 != B or C2 != C:
-        raise ValueError(f"z {tuple(z.shape)} and mean {tuple(mean.shape)} disagree in B or C")
-    if tuple(logstd.shape) != tuple(mean.shape):
-        raise ValueError(f"logstd {tuple(logstd.shape)} must have mean's shape {tuple(mean.shape)}")
-    if C < 1:
-        raise ValueError("C must be at least 1")
+    B, C, Tx, Ty = gaussian_shapes(z, mean, logstd, also=((grad_value, "grad_value must be a [B,T_text,T_mel] tensor"),))
     if tuple(grad_value.shape) != (B, Tx, Ty):
         raise ValueError(f"grad_value {tuple(grad_value.shape)} must be [B,T_text,T_mel] = {(B, Tx, Ty)}")
     if not (need_z or need_mean or need_logstd):
         raise ValueError("at least one of need_z, need_mean, need_logstd must be set")
-    for t, name in ((grad_value, "grad_value"), (z, "z"), (mean, "mean"), (logstd, "logstd")):
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a GPU tensor")
-    dev = z.device
-    if mean.device != dev or logstd.device != dev or grad_value.device != dev:
-        raise ValueError("grad_value, z, mean and logstd must be on the same device")
+    dev = one_gpu(((grad_value, "grad_value"), (z, "z"), (mean, "mean"), (logstd, "logstd")), "grad_value, z, mean and logstd")
     for t, name in ((t_x, "t_x"), (t_y, "t_y"), (grad_scale, "grad_scale")):
-        if t is not None and t.numel() != B:
-            raise ValueError(f"{name} must have one entry per utterance")
+        per_utterance(t, B, name)
     _lib.require_gpu()
     with torch.no_grad(), torch.cuda.device(dev):
-        zc, mc, sc = _f32(z), _f32(mean), _f32(logstd)
+        zc, mc, sc = f32c(z), f32c(mean), f32c(logstd)
         g, ld = _grad_layout(grad_value, B, Tx, Ty)
-        if t_x is not None:
-            t_x = t_x.to(device=dev, dtype=torch.int32).contiguous()
-        if t_y is not None:
-            t_y = t_y.to(device=dev, dtype=torch.int32).contiguous()
+        t_x, t_y = lengths(t_x, B, dev, "t_x"), lengths(t_y, B, dev, "t_y")
         if grad_scale is not None:
             grad_scale = grad_scale.detach().to(device=dev, dtype=torch.float32).contiguous()
         dz = torch.empty((B, C, Ty), dtype=torch.float32, device=dev) if need_z else None
@@ -194,11 +150,8 @@ def gaussian_logp_backward(grad_value: torch.Tensor, z: torch.Tensor, mean: torc
         nws = lib.aligner_gauss_logp_backward_workspace_bytes(B, C, Tx, Ty)
         ws = _workspaces.get(dev, max(nws, 1))
         _lib.check(lib.aligner_gauss_logp_backward_f32(
-            g.data_ptr(), ld, None if grad_scale is None else grad_scale.data_ptr(), zc.data_ptr(), mc.data_ptr(),
-            sc.data_ptr(), None if t_x is None else t_x.data_ptr(), None if t_y is None else t_y.data_ptr(),
-            None if dz is None else dz.data_ptr(), None if dm is None else dm.data_ptr(),
-            None if ds is None else ds.data_ptr(), ws.data_ptr(), ws.numel(), B, C, Tx, Ty,
-            torch.cuda.current_stream(dev).cuda_stream))
+            g.data_ptr(), ld, ptr(grad_scale), zc.data_ptr(), mc.data_ptr(), sc.data_ptr(), ptr(t_x), ptr(t_y),
+            ptr(dz), ptr(dm), ptr(ds), ws.data_ptr(), ws.numel(), B, C, Tx, Ty, stream(dev)))
     return dz, dm, ds
 
 

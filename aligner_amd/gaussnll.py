@@ -21,30 +21,14 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._operands import f32c, gaussian_shapes, lengths, one_gpu, per_utterance, ptr, stream
 from .maxpath import Alignment
 
 _workspaces = _lib.StreamWorkspaces(zero=False)
 
 
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
 def _check(z, mean, logstd, durations, t_y) -> Tuple[int, int, int, int, torch.Tensor]:
-    for t, name in ((z, "z"), (mean, "mean"), (logstd, "logstd")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3:
-            raise ValueError(f"{name} must be a [B,C,T] tensor")
-    B, C, Ty = z.shape
-    B2, C2, Tx = mean.shape
-    if B2 != B or C2 != C:
-        raise ValueError(f"z {tuple(z.shape)} and mean {tuple(mean.shape)} disagree in B or C")
-    if tuple(logstd.shape) != tuple(mean.shape):
-        raise ValueError(f"logstd {tuple(logstd.shape)} must have mean's shape {tuple(mean.shape)}")
-    if C < 1:
-        raise ValueError("C must be at least 1")
+    B, C, Tx, Ty = gaussian_shapes(z, mean, logstd)
     if isinstance(durations, Alignment):
         if durations.durations is None:
             raise ValueError("the Alignment holds no durations (align(..., want_durations=True))")
@@ -54,13 +38,8 @@ def _check(z, mean, logstd, durations, t_y) -> Tuple[int, int, int, int, torch.T
         raise ValueError("durations must be an integer tensor")
     if tuple(durations.shape) != (B, Tx):
         raise ValueError(f"durations must be [B,T_text] = [{B},{Tx}]")
-    if t_y is not None and torch.as_tensor(t_y).numel() != B:
-        raise ValueError("t_y must have one entry per utterance")
-    for t, name in ((z, "z"), (mean, "mean"), (logstd, "logstd")):
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a GPU tensor")
-    if mean.device != z.device or logstd.device != z.device:
-        raise ValueError("z, mean and logstd must be on the same device")
+    per_utterance(t_y, B, "t_y")
+    one_gpu(((z, "z"), (mean, "mean"), (logstd, "logstd")), "z, mean and logstd")
     return B, C, Tx, Ty, durations
 
 
@@ -77,12 +56,9 @@ def _run(zc, mc, sc, dur, ty, scale, want_loss: bool, want_grad: bool):
     ds = torch.empty_like(sc) if want_grad else None
     # (0 bytes: a shape outside the domain; the call itself reports which limit, as an AlignerError of code EDOM)
     ws = _workspaces.get(dev, max(lib.aligner_gauss_nll_workspace_bytes(B, C, Tx), 1))
-
-    def ptr(t):
-        return None if t is None else t.data_ptr()
     _lib.check(lib.aligner_gauss_nll_f32(zc.data_ptr(), mc.data_ptr(), sc.data_ptr(), dur.data_ptr(), ptr(ty), ptr(scale),
                                          ptr(nll), ptr(count), ptr(dz), ptr(dm), ptr(ds), ws.data_ptr(), ws.numel(),
-                                         B, C, Tx, Ty, torch.cuda.current_stream(dev).cuda_stream))
+                                         B, C, Tx, Ty, stream(dev)))
     return nll, count, dz, dm, ds
 
 
@@ -99,8 +75,7 @@ def gaussian_nll(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, dura
     zeros without a launch.  Asynchronous on the current stream."""
     B, C, Tx, Ty, durations = _check(z, mean, logstd, durations, t_y)
     dev = z.device
-    if scale is not None and torch.as_tensor(scale).numel() != B:
-        raise ValueError("scale must have one entry per utterance")
+    per_utterance(scale, B, "scale")
     _lib.require_gpu()
     with torch.no_grad(), torch.cuda.device(dev):
         if B == 0 or Tx == 0 or Ty == 0:
@@ -111,9 +86,9 @@ def gaussian_nll(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor, dura
                         torch.zeros((B, C, Tx), dtype=torch.float32, device=dev))
             return out
         dur = durations.detach().to(device=dev, dtype=torch.int32).contiguous()
-        ty = None if t_y is None else torch.as_tensor(t_y).detach().to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+        ty = lengths(t_y, B, dev, "t_y")
         sc = None if scale is None else torch.as_tensor(scale).detach().to(device=dev, dtype=torch.float32).reshape(B).contiguous()
-        nll, count, dz, dm, ds = _run(_f32(z), _f32(mean), _f32(logstd), dur, ty, sc, True, want_grad)
+        nll, count, dz, dm, ds = _run(f32c(z), f32c(mean), f32c(logstd), dur, ty, sc, True, want_grad)
     return (nll, count, dz, dm, ds) if want_grad else (nll, count)
 
 
@@ -122,7 +97,7 @@ class _GaussNLL(torch.autograd.Function):
     def forward(ctx, z, mean, logstd, dur, ty):
         # (operands checked and converted by gaussian_nll_loss(): straight to the loss-only kernel)
         with torch.no_grad(), torch.cuda.device(z.device):
-            nll, count, _, _, _ = _run(_f32(z), _f32(mean), _f32(logstd), dur, ty, None, True, False)
+            nll, count, _, _, _ = _run(f32c(z), f32c(mean), f32c(logstd), dur, ty, None, True, False)
         ctx.save_for_backward(z, mean, logstd, dur, ty)
         ctx.mark_non_differentiable(count)
         return nll, count
@@ -136,7 +111,7 @@ class _GaussNLL(torch.autograd.Function):
         # the gradient form with scale = g_nll: z is read a second time and dz written once, already scaled
         with torch.no_grad(), torch.cuda.device(z.device):
             sc = g_nll.detach().to(torch.float32).contiguous()
-            _, _, dz, dm, ds = _run(_f32(z), _f32(mean), _f32(logstd), dur, ty, sc, False, True)
+            _, _, dz, dm, ds = _run(f32c(z), f32c(mean), f32c(logstd), dur, ty, sc, False, True)
         need = ctx.needs_input_grad
         return (dz.to(z.dtype) if need[0] else None, dm.to(mean.dtype) if need[1] else None,
                 ds.to(logstd.dtype) if need[2] else None, None, None)
@@ -161,7 +136,7 @@ def gaussian_nll_loss(z: torch.Tensor, mean: torch.Tensor, logstd: torch.Tensor,
     else:
         _lib.require_gpu()
         dur = dur.detach().to(device=dev, dtype=torch.int32).contiguous()
-        ty = None if t_y is None else torch.as_tensor(t_y).detach().to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+        ty = lengths(t_y, B, dev, "t_y")
         nll, count = _GaussNLL.apply(z, mean, logstd, dur, ty)
     if reduction == "none":
         return nll

@@ -21,28 +21,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._operands import f32c, lengths, ptr, stream
 
 _workspaces = _lib.StreamWorkspaces(zero=False)
-
-
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
-def _lengths(t, B: int, dev, name: str) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    t = torch.as_tensor(t)
-    if t.numel() != B:
-        raise ValueError(f"{name} must have one entry per utterance")
-    return t.detach().to(device=dev, dtype=torch.int32).reshape(B).contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _forward(h, c, a, g, tx, ty, off: float, Ty: int) -> torch.Tensor:
@@ -53,9 +34,9 @@ def _forward(h, c, a, g, tx, ty, off: float, Ty: int) -> torch.Tensor:
     out = torch.empty((B, C, Ty), dtype=torch.float32, device=dev)
     # (0 bytes: a shape outside the domain; the call itself reports which limit, as an AlignerError of code EDOM)
     ws = _workspaces.get(dev, max(lib.aligner_gauss_upsample_workspace_bytes(B, C, Tx, Ty), 1))
-    _lib.check(lib.aligner_gauss_upsample_f32(h.data_ptr(), c.data_ptr(), a.data_ptr(), _ptr(g), _ptr(tx), _ptr(ty), off,
+    _lib.check(lib.aligner_gauss_upsample_f32(h.data_ptr(), c.data_ptr(), a.data_ptr(), ptr(g), ptr(tx), ptr(ty), off,
                                               out.data_ptr(), ws.data_ptr(), ws.numel(), B, C, Tx, Ty,
-                                              torch.cuda.current_stream(dev).cuda_stream))
+                                              stream(dev)))
     return out
 
 
@@ -68,10 +49,10 @@ def _backward(h, c, a, g, tx, ty, off: float, gout, want_h: bool, want_c: bool, 
     dh = torch.empty_like(h) if want_h else None
     dc, da, dg = (torch.empty((B, Tx), dtype=torch.float32, device=dev) if w else None for w in (want_c, want_a, want_g))
     ws = _workspaces.get(dev, max(lib.aligner_gauss_upsample_backward_workspace_bytes(B, C, Tx, Ty), 1))
-    _lib.check(lib.aligner_gauss_upsample_backward_f32(h.data_ptr(), c.data_ptr(), a.data_ptr(), _ptr(g), _ptr(tx), _ptr(ty),
-                                                       off, gout.data_ptr(), _ptr(dh), _ptr(dc), _ptr(da), _ptr(dg),
+    _lib.check(lib.aligner_gauss_upsample_backward_f32(h.data_ptr(), c.data_ptr(), a.data_ptr(), ptr(g), ptr(tx), ptr(ty),
+                                                       off, gout.data_ptr(), ptr(dh), ptr(dc), ptr(da), ptr(dg),
                                                        ws.data_ptr(), ws.numel(), B, C, Tx, Ty,
-                                                       torch.cuda.current_stream(dev).cuda_stream))
+                                                       stream(dev)))
     return dh, dc, da, dg
 
 
@@ -80,7 +61,7 @@ class _GaussUp(torch.autograd.Function):
     def forward(ctx, h, c, a, g, tx, ty, off, Ty):
         # (operands checked by gaussian_upsample_at(); a and g already have the centres' shape)
         with torch.no_grad(), torch.cuda.device(h.device):
-            out = _forward(_f32(h), _f32(c), _f32(a), None if g is None else _f32(g), tx, ty, off, Ty)
+            out = _forward(f32c(h), f32c(c), f32c(a), None if g is None else f32c(g), tx, ty, off, Ty)
         ctx.save_for_backward(h, c, a, g, tx, ty)
         ctx.off = off
         return out if h.dtype == torch.float32 else out.to(h.dtype)
@@ -94,8 +75,8 @@ class _GaussUp(torch.autograd.Function):
         if not (need[0] or need[1] or need[2] or need_g):
             return (None,) * 8
         with torch.no_grad(), torch.cuda.device(h.device):
-            dh, dc, da, dg = _backward(_f32(h), _f32(c), _f32(a), None if g is None else _f32(g), tx, ty, ctx.off,
-                                       _f32(gout), need[0], need[1], need[2], need_g)
+            dh, dc, da, dg = _backward(f32c(h), f32c(c), f32c(a), None if g is None else f32c(g), tx, ty, ctx.off,
+                                       f32c(gout), need[0], need[1], need[2], need_g)
         return (None if dh is None else dh.to(h.dtype), None if dc is None else dc.to(c.dtype),
                 None if da is None else da.to(a.dtype), None if dg is None else dg.to(g.dtype), None, None, None, None)
 
@@ -143,8 +124,8 @@ def gaussian_upsample_at(h: torch.Tensor, centres: torch.Tensor, precision, log_
     a = _row_operand(precision, centres, "precision")
     g = None if log_weight is None else _row_operand(log_weight, centres, "log_weight")
     dev = h.device
-    tx = _lengths(t_x, B, dev, "t_x")
-    ty = _lengths(t_y, B, dev, "t_y")
+    tx = lengths(t_x, B, dev, "t_x")
+    ty = lengths(t_y, B, dev, "t_y")
     if B == 0 or C == 0 or Tx == 0 or Ty == 0:
         out = torch.zeros((B, C, Ty), dtype=h.dtype, device=dev)
         live = [t for t in (h, centres, a, g) if isinstance(t, torch.Tensor) and t.requires_grad]

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._operands import ptr, stream
 
 _TORCH_TO_DT = {
     torch.float32: _lib.DT_F32, torch.float16: _lib.DT_F16, torch.bfloat16: _lib.DT_BF16,
@@ -48,14 +49,6 @@ def _device_for(t: torch.Tensor) -> torch.device:
 
 def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
     return _workspaces.get(device, nbytes)             # one per (device, stream): calls on two streams never share
-
-
-def _stream_ptr(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 def align(value: torch.Tensor, t_x: Optional[torch.Tensor] = None, t_y: Optional[torch.Tensor] = None, *,
@@ -166,12 +159,12 @@ def align(value: torch.Tensor, t_x: Optional[torch.Tensor] = None, t_y: Optional
                     int(_test_flags)
             if ld != Ty:
                 _lib.check(lib.aligner_maxpath_ld(
-                    v.data_ptr(), _TORCH_TO_DT[v.dtype], ld, _ptr(t_x), _ptr(t_y), _ptr(path), pdt, _ptr(tok), _ptr(dur),
-                    ws.data_ptr(), ws.numel(), B, Tx, Ty, float(max_neg_val), flags, _stream_ptr(device)))
+                    v.data_ptr(), _TORCH_TO_DT[v.dtype], ld, ptr(t_x), ptr(t_y), ptr(path), pdt, ptr(tok), ptr(dur),
+                    ws.data_ptr(), ws.numel(), B, Tx, Ty, float(max_neg_val), flags, stream(device)))
             else:
                 _lib.check(lib.aligner_maxpath(
-                    v.data_ptr(), _TORCH_TO_DT[v.dtype], _ptr(m), mdt, _ptr(t_x), _ptr(t_y), _ptr(path), pdt, _ptr(tok), _ptr(dur),
-                    ws.data_ptr(), ws.numel(), B, Tx, Ty, float(max_neg_val), flags, _stream_ptr(device)))
+                    v.data_ptr(), _TORCH_TO_DT[v.dtype], ptr(m), mdt, ptr(t_x), ptr(t_y), ptr(path), pdt, ptr(tok), ptr(dur),
+                    ws.data_ptr(), ws.numel(), B, Tx, Ty, float(max_neg_val), flags, stream(device)))
         else:
             for t in (path, tok, dur):
                 if t is not None:
@@ -210,7 +203,7 @@ def read_status(device=None) -> int:
     with torch.cuda.device(device):
         torch.cuda.synchronize(device)
         for ws in _workspaces.on_device(device):
-            _lib.check(_lib.load().aligner_maxpath_read_status(ws.data_ptr(), out.ctypes.data, _stream_ptr(device)))
+            _lib.check(_lib.load().aligner_maxpath_read_status(ws.data_ptr(), out.ctypes.data, stream(device)))
             st |= int(out[0])
     return st
 
@@ -242,7 +235,7 @@ def _maximum_path_resident(value: torch.Tensor, mask: torch.Tensor, mask_is_pref
         rc = lib.aligner_maxpath(value.data_ptr(), dt, mask.data_ptr(), dt, None, None, path.data_ptr(), dt, None, None,
                                  ws.data_ptr(), ws.numel(), B, Tx, Ty, -1e9,
                                  (0 if mask_is_prefix else _lib.F_STRICT_MASK) | _lib.F_COMPAT_TXGTTY,
-                                 torch.cuda.current_stream(device).cuda_stream)
+                                 stream(device))
         if rc:
             _lib.check(rc)
     finally:

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._operands import ptr, stream
 
 _DT = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
 _workspaces = _lib.StreamWorkspaces(zero=True)
@@ -62,10 +63,7 @@ def boundary_search(energies: torch.Tensor, t_x: torch.Tensor, t_y: torch.Tensor
             ws = _workspaces.get(dev, need)
             _lib.check(lib.aligner_boundary_search(
                 e.data_ptr(), _DT[e.dtype], tx.data_ptr(), ty.data_ptr(), int(max_duration),
-                None if bnd is None else bnd.data_ptr(), None if dur is None else dur.data_ptr(),
-                None if score is None else score.data_ptr(), None if la is None else la.data_ptr(),
-                None if ga is None else ga.data_ptr(), ws.data_ptr(), ws.numel(), B, Tx, Ty,
-                torch.cuda.current_stream(dev).cuda_stream))
+                ptr(bnd), ptr(dur), ptr(score), ptr(la), ptr(ga), ws.data_ptr(), ws.numel(), B, Tx, Ty, stream(dev)))
     return BoundarySearch(bnd, dur, score, la, ga)
 
 
@@ -115,8 +113,7 @@ def boundary_search_backward(energies: torch.Tensor, t_x: torch.Tensor, t_y: tor
             ws = _bwd_workspaces.get(dev, need)
             _lib.check(lib.aligner_boundary_search_backward(
                 e.data_ptr(), _DT[e.dtype], tx.data_ptr(), ty.data_ptr(), int(max_duration), la.data_ptr(),
-                None if gla is None else gla.data_ptr(), None if gga is None else gga.data_ptr(), grad.data_ptr(),
-                ws.data_ptr(), ws.numel(), B, Tx, Ty, torch.cuda.current_stream(dev).cuda_stream))
+                ptr(gla), ptr(gga), grad.data_ptr(), ws.data_ptr(), ws.numel(), B, Tx, Ty, stream(dev)))
     return grad
 
 
@@ -165,6 +162,6 @@ def read_status(device=None) -> int:
         torch.cuda.synchronize(device)
         for ws in list(_workspaces.on_device(device)) + list(_bwd_workspaces.on_device(device)):
             _lib.check(_lib.load().aligner_maxpath_read_status(ws.data_ptr(), out.ctypes.data,
-                                                               torch.cuda.current_stream(device).cuda_stream))
+                                                               stream(device)))
             st |= int(out[0])
     return st

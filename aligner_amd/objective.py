@@ -19,7 +19,8 @@ import torch
 
 from . import _lib
 from .maxpath import Alignment
-from .softattn import _chk, _stream
+from ._operands import lengths, ptr, stream
+from .softattn import _chk
 
 _fs_workspaces = _lib.StreamWorkspaces(zero=False, slack=1.0)
 
@@ -28,11 +29,11 @@ def _fs_workspace(device, nbytes: int) -> torch.Tensor:
     return _fs_workspaces.get(device, nbytes)          # one per (device, stream)
 
 
-def _lengths(t: torch.Tensor, name: str, B: int, dev) -> torch.Tensor:
-    t = torch.as_tensor(t).detach().to(device=dev, dtype=torch.int32).contiguous()
-    if t.shape != (B,):
+def _lengths(t, B: int, dev, name: str) -> torch.Tensor:
+    """lengths(), for the entry points that require t_x / t_y and take them as [B] only."""
+    if torch.as_tensor(t).shape != (B,):
         raise ValueError(f"{name} must have shape [{B}]")
-    return t
+    return lengths(t, B, dev, name)
 
 
 def forward_sum(logp: torch.Tensor, t_x: torch.Tensor, t_y: torch.Tensor, want_grad: bool = True,
@@ -49,8 +50,8 @@ def forward_sum(logp: torch.Tensor, t_x: torch.Tensor, t_y: torch.Tensor, want_g
         raise ValueError("logp must be [B, T_text, T_mel]")
     B, Tx, Ty = lp.shape
     dev = lp.device
-    tx = _lengths(t_x, "t_x", B, dev)
-    ty = _lengths(t_y, "t_y", B, dev)
+    tx = _lengths(t_x, B, dev, "t_x")
+    ty = _lengths(t_y, B, dev, "t_y")
     lib = _lib.load()
     ctc = blank_logprob is not None
     nws = (lib.aligner_forward_sum_ctc_workspace_bytes if ctc else lib.aligner_forward_sum_workspace_bytes)(B, Tx, Ty)
@@ -62,13 +63,12 @@ def forward_sum(logp: torch.Tensor, t_x: torch.Tensor, t_y: torch.Tensor, want_g
     if ctc:
         with torch.cuda.device(dev):
             _lib.check(lib.aligner_forward_sum_ctc_f32(lp.data_ptr(), tx.data_ptr(), ty.data_ptr(), float(blank_logprob),
-                                                       loss.data_ptr(), None if grad is None else grad.data_ptr(),
-                                                       ws.data_ptr(), ws.numel(), B, Tx, Ty, _stream(dev)))
+                                                       loss.data_ptr(), ptr(grad), ws.data_ptr(), ws.numel(), B, Tx, Ty,
+                                                       stream(dev)))
         return loss, grad
     with torch.cuda.device(dev):
         _lib.check(lib.aligner_forward_sum_f32(lp.data_ptr(), tx.data_ptr(), ty.data_ptr(), loss.data_ptr(),
-                                               None if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               B, Tx, Ty, _stream(dev)))
+                                               ptr(grad), ws.data_ptr(), ws.numel(), B, Tx, Ty, stream(dev)))
     return loss, grad
 
 
@@ -123,12 +123,12 @@ def beta_binomial_prior(t_x: torch.Tensor, t_y: torch.Tensor, T_text: int, T_mel
         raise ValueError("t_x must be a GPU tensor")
     dev = t_x.device
     B = t_x.shape[0]
-    tx = _lengths(t_x, "t_x", B, dev)
-    ty = _lengths(t_y, "t_y", B, dev)
+    tx = _lengths(t_x, B, dev, "t_x")
+    ty = _lengths(t_y, B, dev, "t_y")
     out = torch.empty((B, T_text, T_mel), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().aligner_beta_binomial_prior_f32(tx.data_ptr(), ty.data_ptr(), out.data_ptr(), B, T_text,
-                                                               T_mel, float(scaling), _stream(dev)))
+                                                               T_mel, float(scaling), stream(dev)))
     return out
 
 
@@ -146,8 +146,7 @@ def _regulate(hh: torch.Tensor, dur: torch.Tensor, T_mel: int, want_tok: bool = 
     tok = torch.empty((B, T_mel), dtype=torch.int32, device=dev) if want_tok else None
     with torch.cuda.device(dev):
         _lib.check(_lib.load().aligner_regulate_f32(hh.data_ptr(), dur.data_ptr(), out.data_ptr(),
-                                                    None if tok is None else tok.data_ptr(),
-                                                    B, C, Tx, T_mel, _stream(dev)))
+                                                    ptr(tok), B, C, Tx, T_mel, stream(dev)))
     return out, tok
 
 
@@ -169,7 +168,7 @@ def segment_reduce(frames: torch.Tensor, durations: torch.Tensor, mean: bool = F
     out = torch.empty((B, C, Tx), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().aligner_segment_reduce_f32(ff.data_ptr(), dur.data_ptr(), out.data_ptr(), B, C, Tx, Ty,
-                                                          1 if mean else 0, _stream(dev)))
+                                                          1 if mean else 0, stream(dev)))
     return out
 
 
@@ -290,8 +289,8 @@ def _bin_loss(lp: torch.Tensor, ld: int, tok: torch.Tensor, ty: Optional[torch.T
     count = torch.empty((B,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().aligner_bin_loss(lp.data_ptr(), _LOGP_DTYPES[lp.dtype], ld, tok.data_ptr(),
-                                                None if ty is None else ty.data_ptr(), float(min_logp),
-                                                nll.data_ptr(), count.data_ptr(), B, Tx, Ty, _stream(dev)))
+                                                ptr(ty), float(min_logp), nll.data_ptr(), count.data_ptr(), B, Tx, Ty,
+                                                stream(dev)))
     return nll, count
 
 
@@ -303,7 +302,7 @@ def bin_loss(logp: torch.Tensor, tok: torch.Tensor, t_y: Optional[torch.Tensor] 
     lp, ld = _logp_in_place(logp)
     B, Tx, Ty = lp.shape
     tok = _hard_tok(tok, B, Tx, Ty, lp.device)
-    ty = None if t_y is None else _lengths(t_y, "t_y", B, lp.device)
+    ty = None if t_y is None else _lengths(t_y, B, lp.device, "t_y")
     return _bin_loss(lp, ld, tok, ty, min_logp)
 
 
@@ -312,9 +311,9 @@ def _bin_loss_grad(lp, ld, tok, ty, min_logp, scale, grad, accumulate):
     dev = lp.device
     with torch.cuda.device(dev):
         _lib.check(_lib.load().aligner_bin_loss_grad_f32(lp.data_ptr(), _LOGP_DTYPES[lp.dtype], ld, tok.data_ptr(),
-                                                         None if ty is None else ty.data_ptr(), float(min_logp),
+                                                         ptr(ty), float(min_logp),
                                                          scale.data_ptr(), grad.data_ptr(), 1 if accumulate else 0,
-                                                         B, Tx, Ty, _stream(dev)))
+                                                         B, Tx, Ty, stream(dev)))
 
 
 class _BinLoss(torch.autograd.Function):
@@ -357,7 +356,7 @@ def binarization_loss(logp: torch.Tensor, hard, t_y: Optional[torch.Tensor] = No
         raise ValueError("logp must be [B, T_text, T_mel]")
     B, Tx, Ty = logp.shape
     tok = _hard_tok(hard, B, Tx, Ty, logp.device)
-    ty = None if t_y is None else _lengths(t_y, "t_y", B, logp.device)
+    ty = None if t_y is None else _lengths(t_y, B, logp.device, "t_y")
     nll, count = _BinLoss.apply(logp, tok, ty, float(min_logp))
     if reduction == "none":
         return nll
@@ -373,7 +372,7 @@ class _AlignmentLoss(torch.autograd.Function):
         lp = _chk(logp, "logp")
         B = lp.shape[0]
         loss, grad = forward_sum(lp, t_x, t_y, want_grad=need, blank_logprob=blank_logprob)
-        ty = _lengths(t_y, "t_y", B, lp.device)
+        ty = _lengths(t_y, B, lp.device, "t_y")
         nll, count = _bin_loss(lp, lp.shape[2], tok, ty, min_logp)
         n = count.sum().clamp_min(1)
         fs_part = loss.mean()

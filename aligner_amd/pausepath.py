@@ -15,7 +15,8 @@ from typing import NamedTuple, Optional, Union
 import torch
 
 from . import _lib
-from .maxpath import _SCORE_DTYPES, _TORCH_TO_DT, _ptr, _stream_ptr
+from ._operands import ptr, stream
+from .maxpath import _SCORE_DTYPES, _TORCH_TO_DT
 
 _workspaces = _lib.StreamWorkspaces(zero=False)      # decision words only: no status word, nothing to keep
 
@@ -99,9 +100,9 @@ def align_with_pauses(value: torch.Tensor, t_x: torch.Tensor, t_y: torch.Tensor,
             nbytes = lib.aligner_pausepath_workspace_bytes(B, Tx, Ty)
             ws = _workspaces.get(device, nbytes) if nbytes else None
             _lib.check(lib.aligner_pausepath(
-                v.data_ptr(), _TORCH_TO_DT[v.dtype], ld, _ptr(pz), pause_score, _ptr(gm), t_x.data_ptr(), t_y.data_ptr(),
-                _ptr(tok), _ptr(dur), _ptr(pauses), _ptr(sdur), _ptr(score),
-                _ptr(ws), ws.numel() if ws is not None else 0, B, Tx, Ty, _stream_ptr(device)))
+                v.data_ptr(), _TORCH_TO_DT[v.dtype], ld, ptr(pz), pause_score, ptr(gm), t_x.data_ptr(), t_y.data_ptr(),
+                ptr(tok), ptr(dur), ptr(pauses), ptr(sdur), ptr(score),
+                ptr(ws), ws.numel() if ws is not None else 0, B, Tx, Ty, stream(device)))
         else:
             # no launch: an empty batch, or utterances without a path (Tx == 0 or Ty == 0) -- the outputs the kernel
             # gives an infeasible utterance

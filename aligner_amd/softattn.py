@@ -20,15 +20,13 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib
+from ._operands import f32c, ptr, stream
 
 
 def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
     if not t.is_cuda:
         raise ValueError(f"{name} must be a GPU tensor")
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+    return f32c(t)
 
 
 _workspaces = _lib.StreamWorkspaces(zero=False)
@@ -42,10 +40,6 @@ def _workspace(device, nbytes: int) -> torch.Tensor:
     return _workspaces.get(device, nbytes)             # one per (device, stream)
 
 
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _prepared_weights(weight: torch.Tensor, device) -> torch.Tensor:
     """weights -> split bf16 halves in the matrix cores' fragment order (aligner_conv1d_prepare_f32, a few
     microseconds), kept per weight tensor (and stream: no cross-stream ordering) until the tensor is modified in place
@@ -54,14 +48,14 @@ def _prepared_weights(weight: torch.Tensor, device) -> torch.Tensor:
     invalidate_prepared() after such an update."""
     lib = _lib.load()
     Cout, Cin, K = weight.shape
-    key = (weight.data_ptr(), Cout, Cin, K, device, _stream(device))
+    key = (weight.data_ptr(), Cout, Cin, K, device, stream(device))
     ent = _prepared.get(key)
     if ent is None or ent[0] != weight._version:
         nprep = lib.aligner_conv1d_prepared_bytes(Cout, Cin, K)
         if nprep == 0:
             raise ValueError(f"kernel size {K} not supported (1, 3, 5)")
         prep = ent[1] if ent is not None else torch.empty(nprep, dtype=torch.uint8, device=device)
-        _lib.check(lib.aligner_conv1d_prepare_f32(weight.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K, _stream(device)))
+        _lib.check(lib.aligner_conv1d_prepare_f32(weight.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K, stream(device)))
         if ent is None and len(_prepared) >= 256:
             _prepared.pop(next(iter(_prepared)))       # oldest entry only
         _prepared[key] = (weight._version, prep, weight)   # holding `weight` keeps its address from being reused
@@ -97,9 +91,8 @@ def _conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
         nws = lib.aligner_conv1d_workspace_bytes(B, Cin, Cout, T, K)
         ws = _conv_workspaces.get(x.device, nws) if nws else None
         _lib.check(lib.aligner_conv1d_prepared_ws_f32(x.data_ptr(), prep.data_ptr(),
-                                                      None if bias is None else bias.data_ptr(), y.data_ptr(),
-                                                      None if ws is None else ws.data_ptr(), nws,
-                                                      B, Cin, Cout, T, K, int(relu), _stream(x.device)))
+                                                      ptr(bias), y.data_ptr(), ptr(ws), nws,
+                                                      B, Cin, Cout, T, K, int(relu), stream(x.device)))
     return y
 
 
@@ -109,7 +102,7 @@ def _prepared_weights_transposed(weight: torch.Tensor, device) -> torch.Tensor:
     own, re-prepared when the weight's version counter moves."""
     lib = _lib.load()
     Cout, Cin, K = weight.shape
-    key = (weight.data_ptr(), Cout, Cin, K, device, _stream(device))
+    key = (weight.data_ptr(), Cout, Cin, K, device, stream(device))
     ent = _prepared_t.get(key)
     if ent is None or ent[0] != weight._version:
         nprep = lib.aligner_conv1d_prepared_bytes(Cin, Cout, K)
@@ -117,7 +110,7 @@ def _prepared_weights_transposed(weight: torch.Tensor, device) -> torch.Tensor:
             raise ValueError(f"kernel size {K} not supported (1, 3, 5)")
         prep = ent[1] if ent is not None else torch.empty(nprep, dtype=torch.uint8, device=device)
         _lib.check(lib.aligner_conv1d_prepare_transposed_f32(weight.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K,
-                                                             _stream(device)))
+                                                             stream(device)))
         if ent is None and len(_prepared_t) >= 256:
             _prepared_t.pop(next(iter(_prepared_t)))
         _prepared_t[key] = (weight._version, prep, weight)
@@ -160,17 +153,14 @@ def conv1d_backward(x: torch.Tensor, weight: torch.Tensor, y: Optional[torch.Ten
             ws = _bwd_workspaces.get(dev, nws) if (need_w or need_b) and nws else None
             _lib.check(lib.aligner_conv1d_backward_weight_f32(
                 x.data_ptr(), y.data_ptr() if relu else None, gy.data_ptr(), gyp.data_ptr() if (relu and need_x) else None,
-                None if gw is None else gw.data_ptr(), None if gb is None else gb.data_ptr(),
-                None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
-                B, Cin, Cout, T, K, int(relu), _stream(dev)))
+                ptr(gw), ptr(gb), ptr(ws), 0 if ws is None else ws.numel(), B, Cin, Cout, T, K, int(relu), stream(dev)))
         if need_x:
             prep = _prepared_weights_transposed(weight, dev)
             gx = torch.empty((B, Cin, T), dtype=torch.float32, device=dev)
             nws = lib.aligner_conv1d_workspace_bytes(B, Cout, Cin, T, K)
             ws = _conv_workspaces.get(dev, nws) if nws else None
             _lib.check(lib.aligner_conv1d_prepared_ws_f32(gyp.data_ptr(), prep.data_ptr(), None, gx.data_ptr(),
-                                                          None if ws is None else ws.data_ptr(), nws,
-                                                          B, Cout, Cin, T, K, 0, _stream(dev)))
+                                                          ptr(ws), nws, B, Cout, Cin, T, K, 0, stream(dev)))
     return gx, gw, gb
 
 
@@ -271,11 +261,9 @@ def _soft_attention(keys_enc, queries_enc, t_x, prior, temperature, sim, want_so
     with torch.cuda.device(dev):
         ws = _workspace(dev, lib.aligner_softattn_workspace_bytes(B, C, Tx))
         _lib.check(lib.aligner_softattn_ld(
-            k.data_ptr(), q.data_ptr(), None if t_x is None else t_x.data_ptr(),
-            None if prior is None else prior.data_ptr(), logp.data_ptr(),
+            k.data_ptr(), q.data_ptr(), ptr(t_x), ptr(prior), logp.data_ptr(),
             _lib.DT_BF16 if logp_dtype == torch.bfloat16 else _lib.DT_F32, ld,
-            None if soft is None else soft.data_ptr(), ws.data_ptr(), ws.numel(),
-            B, C, Tx, Ty, float(temperature), simc, _stream(dev)))
+            ptr(soft), ws.data_ptr(), ws.numel(), B, C, Tx, Ty, float(temperature), simc, stream(dev)))
     return logp, soft
 
 
@@ -318,10 +306,8 @@ def soft_attention_backward(keys_enc: torch.Tensor, queries_enc: torch.Tensor, g
     with torch.cuda.device(dev):
         ws = _bwd_workspaces.get(dev, lib.aligner_softattn_backward_workspace_bytes(B, C, Tx, Ty))
         _lib.check(lib.aligner_softattn_backward_f32(
-            k.data_ptr(), q.data_ptr(), None if t_x is None else t_x.data_ptr(), None if prior is None else prior.data_ptr(),
-            gl.data_ptr(), None if gs is None else gs.data_ptr(), None if gk is None else gk.data_ptr(),
-            None if gq is None else gq.data_ptr(), ws.data_ptr(), ws.numel(), B, C, Tx, Ty, float(temperature), simc,
-            _stream(dev)))
+            k.data_ptr(), q.data_ptr(), ptr(t_x), ptr(prior), gl.data_ptr(), ptr(gs), ptr(gk), ptr(gq),
+            ws.data_ptr(), ws.numel(), B, C, Tx, Ty, float(temperature), simc, stream(dev)))
     return gk, gq
 
 
@@ -410,7 +396,7 @@ def encode(x: torch.Tensor, stack: List[Tuple[torch.Tensor, torch.Tensor]]) -> t
                 raise ValueError("channel mismatch")
             prep = _prepared_weights(w, dev)
             keep += [w, b, prep]
-            layers[n] = _lib.ConvLayer(prep.data_ptr(), None if b is None else b.data_ptr(), int(w.shape[1]), int(w.shape[0]),
+            layers[n] = _lib.ConvLayer(prep.data_ptr(), ptr(b), int(w.shape[1]), int(w.shape[0]),
                                        int(w.shape[2]), int(n + 1 < len(stack)))
             c = int(w.shape[0])
         nws = lib.aligner_conv_stack_workspace_bytes(layers, len(stack), B, T) if B > 0 and len(stack) > 0 else 0
@@ -418,7 +404,7 @@ def encode(x: torch.Tensor, stack: List[Tuple[torch.Tensor, torch.Tensor]]) -> t
             y = torch.empty((B, c, T), dtype=torch.float32, device=dev)
             ws = _conv_workspaces.get(dev, nws)
             _lib.check(lib.aligner_conv_stack_f32(x.data_ptr(), layers, len(stack), y.data_ptr(), ws.data_ptr(), nws, B, T,
-                                                  _stream(dev)))
+                                                  stream(dev)))
             return y
     for n, (w, b) in enumerate(stack):
         x = conv1d(x, w, b, relu=(n + 1 < len(stack)))
