@@ -367,7 +367,42 @@ __device__ __forceinline__ unsigned mb_ring_load(const unsigned *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// what the two forms of the chain kernel share: one position of phase 1 / phase 2
+// The segment geometry, shared by the search's chain kernels and the gradient's (mobo_bwd.inc, which numbers the segments
+// from the right).  Three straight-line steps, so that a kernel keeps its two early returns between them:
+// an utterance's clamped lengths (false: infeasible, no segmentation exists) ...
+__device__ __forceinline__ bool mb_lengths(const int *t_xs, const int *t_ys, int Tx, int Ty, int D, int b, int &I, int &J) {
+    I = t_xs[b];
+    J = t_ys[b];
+    I = I > Tx ? Tx : I;
+    J = J > Ty ? Ty : J;
+    return I >= 1 && J >= I && (long long)J <= (long long)I * D;
+}
+// ... its cut into Sb segments of n positions: every one but the last holds n >= D, so a halo has one source ...
+__device__ __forceinline__ void mb_cut(int J, int D, int S, int &Sb, int &n) {
+    const int P = J + 1;
+    Sb = P / D;
+    Sb = Sb < 1 ? 1 : (Sb > S ? S : Sb);
+    n = (P + Sb - 1) / Sb;
+}
+// ... and segment sg of the search: positions [a, bnd) of the J + 1.
+struct MbGeom {
+    int a, bnd;
+    bool empty;               // the utterance has fewer segments than the launch: nothing here
+    bool has_next;            // a segment follows and awaits this one's last D entries (never after `drop_seg`)
+};
+__device__ __forceinline__ MbGeom mb_segment(int J, int D, int S, int sg, int drop_seg) {
+    MbGeom g;
+    int Sb, n;
+    mb_cut(J, D, S, Sb, n);
+    const int P = J + 1;
+    g.a = sg * n;
+    g.empty = sg >= Sb || g.a >= P;
+    g.bnd = (g.a + n < P) ? g.a + n : P;
+    g.has_next = (sg + 1 < Sb) && (g.a + n < P) && sg != drop_seg;
+    return g;
+}
+
+// the several-positions kernel: where one position of phase 1 / phase 2 finds its segment, its LDS arrays and its ring rows
 struct MbSeg {
     int a, bnd, D, J, W;
     bool has_next;
@@ -416,71 +451,52 @@ __device__ __forceinline__ void mb_phase2(const MbSeg &g, int bo, int j, int lo,
     }
 }
 
-// MULTI = false: at most one position per thread -- the form of a split utterance (a segment per CU): the state
-//   of a position lives in registers and the next row's operands (energy, normaliser, halo) are in flight while
-//   this row is computed.  MULTI = true: any number of positions per thread, state in LDS, operands loaded where
-//   they are used -- the form of a large batch, where a CU's many waves hide the latency.
-template <int VT, bool MULTI>
+// Any number of positions per thread, state in LDS, operands loaded where they are used -- the form of a large batch
+// (or of a window too long for the split form), where a CU's many waves hide the latency.
+template <int VT>
 __global__ __launch_bounds__(1024) void mobo_chain_kernel(MoboParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, T = blockDim.x;
     const int b = blockIdx.x / p.S, sg = blockIdx.x - b * p.S;
     const int D = p.D;
-    int I = p.t_xs[b], J = p.t_ys[b];
-    I = I > p.Tx ? p.Tx : I;
-    J = J > p.Ty ? p.Ty : J;
-    const bool ok = I >= 1 && J >= I && (long long)J <= (long long)I * D;
-    if (!ok) {                                     // infeasible: no segmentation exists (outputs: the other kernels)
+    int I, J;
+    if (!mb_lengths(p.t_xs, p.t_ys, p.Tx, p.Ty, D, b, I, J)) {      // (outputs: the other kernels)
         if (sg == 0 && tid == 0) atomicOr(p.status, ALIGNER_ST_BAD_LENGTHS);
         return;
     }
-    // this utterance's segments: every one but the last holds n >= D positions, so a halo has one source
-    const int P = J + 1;
-    int Sb = P / D;
-    Sb = Sb < 1 ? 1 : (Sb > p.S ? p.S : Sb);
-    const int n = (P + Sb - 1) / Sb;
-    const int a = sg * n;
-    if (sg >= Sb || a >= P) return;
+    const MbGeom geom = mb_segment(J, D, p.S, sg, p.drop_seg);
+    if (geom.empty) return;
+    const int a = geom.a;
     MbSeg g;
     g.a = a;
-    g.bnd = (a + n < P) ? a + n : P;
-    g.D = D;
+    g.bnd = geom.bnd;
+    g.has_next = geom.has_next;
     g.J = J;
+    g.D = D;
     g.W = p.nmax + D;                              // entries per buffer
-    g.has_next = (sg + 1 < Sb) && (a + n < P) && sg != p.drop_seg;
     g.sM = reinterpret_cast<int *>(smem);
     g.sS = reinterpret_cast<float *>(g.sM + 2 * g.W);
     g.sV = g.sS + 2 * g.W;
-    float *sLa = g.sV + 2 * g.W, *sDe = sLa + p.nmax;     // MULTI only
+    float *sLa = g.sV + 2 * g.W, *sDe = sLa + p.nmax;
     const int bnd = g.bnd, W = g.W;
     for (int h = tid; h < D; h += T) {             // positions before the utterance's start (segment 0 keeps these)
         g.sM[h] = MB_DEADM;  g.sM[W + h] = MB_DEADM;
         g.sS[h] = 0.f;       g.sS[W + h] = 0.f;
         g.sV[h] = MB_NEG;    g.sV[W + h] = MB_NEG;
     }
-    const int j1 = a + tid;                        // !MULTI: this thread's position
-    float la = (j1 == 0) ? 0.f : MB_NEG, de = la;  // P(b_-1 = 0) = 1
-    if (MULTI)
-        for (int j = j1; j < bnd; j += T) {
-            sLa[j - a] = (j == 0) ? 0.f : MB_NEG;
-            sDe[j - a] = (j == 0) ? 0.f : MB_NEG;
-        }
+    const int j1 = a + tid;
+    for (int j = j1; j < bnd; j += T) {            // P(b_-1 = 0) = 1
+        sLa[j - a] = (j == 0) ? 0.f : MB_NEG;
+        sDe[j - a] = (j == 0) ? 0.f : MB_NEG;
+    }
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     unsigned short *backb = p.back + (size_t)b * p.Tx * p.bstride;
     g.ring_out = p.ring + ((size_t)b * (p.S - 1) + (g.has_next ? sg : 0)) * (size_t)p.Tx * 3 * D;
     const unsigned *ring_in = p.ring + ((size_t)b * (p.S - 1) + (sg > 0 ? sg - 1 : 0)) * (size_t)p.Tx * 3 * D;
     const bool polls = sg > 0 && tid < D;
 
-    unsigned e_nx = 0, h_nx[3] = {0, 0, 0};
-    float L_nx = MB_NEG;
-    auto issue = [&](int i) {                      // row i's operands, in flight while row i-1 is computed
-        const size_t ro = ubase + (size_t)i * p.Ty;
-        if (!MULTI) {
-            const int j = j1 < 1 ? 1 : (j1 > J ? J : j1);
-            const int k = j1 > J - 1 ? J - 1 : j1;
-            e_nx = mb_load_raw<VT>(p.e, ro + (j - 1));
-            L_nx = p.Lw[ro + k];
-        }
+    unsigned h_nx[3] = {0, 0, 0};
+    auto issue = [&](int i) {                      // row i's halo, in flight while row i-1 is computed
         if (polls) {
             const unsigned *r = ring_in + (size_t)i * 3 * D + tid;
             h_nx[0] = mb_ring_load(r);
@@ -497,8 +513,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_kernel(MoboParams p) {
         const long long reach = (long long)(i + 1) * D;
         const int hi2 = hi < reach ? hi : (int)reach;
         const bool active = lo < bnd && hi2 >= a && lo <= hi2;      // some position of the segment is reachable
-        const unsigned e_c = e_nx, h_c0 = h_nx[0], h_c1 = h_nx[1], h_c2 = h_nx[2];
-        const float L_c = L_nx;
+        const unsigned h_c0 = h_nx[0], h_c1 = h_nx[1], h_c2 = h_nx[2];
         if (i + 1 < I) issue(i + 1);
         const size_t ro = ubase + (size_t)i * p.Ty;
         const int bo = (i & 1) * W;
@@ -506,13 +521,9 @@ __global__ __launch_bounds__(1024) void mobo_chain_kernel(MoboParams p) {
         // long as row i-1 had a reachable position here, whether or not row i has one
         if (active || prev_active) {
             // ---- phase 1: u = la_{i-1}(k) - L_i(k), v = delta_{i-1}(k) - L_i(k) for the segment's own positions ----
-            if (!MULTI) {
-                if (j1 < bnd) mb_phase1(g, i, bo, j1, la, de, L_c);
-            } else {
 #pragma unroll 1
-                for (int k = j1; k < bnd; k += T)
-                    mb_phase1(g, i, bo, k, sLa[k - a], sDe[k - a], p.Lw[ro + (k > J - 1 ? J - 1 : k)]);
-            }
+            for (int k = j1; k < bnd; k += T)
+                mb_phase1(g, i, bo, k, sLa[k - a], sDe[k - a], p.Lw[ro + (k > J - 1 ? J - 1 : k)]);
         } else if (g.has_next) {
             for (int h = tid; h < D; h += T) {
                 unsigned *r = g.ring_out + (size_t)i * 3 * D + h;
@@ -548,28 +559,24 @@ __global__ __launch_bounds__(1024) void mobo_chain_kernel(MoboParams p) {
             // ---- phase 2: the windows [j-D, j) ----
 #pragma unroll 1
             for (int j = j1; j < bnd; j += T) {
-                float ev;
-                if (!MULTI) ev = mb_value<VT>(e_c) * MB_LOG2E;
-                else ev = (j >= lo && j <= hi) ? mb_value<VT>(mb_load_raw<VT>(p.e, ro + (j - 1))) * MB_LOG2E : MB_NEG;
+                const float ev = (j >= lo && j <= hi) ? mb_value<VT>(mb_load_raw<VT>(p.e, ro + (j - 1))) * MB_LOG2E : MB_NEG;
                 float lav, dev;
                 int dur;
                 mb_phase2(g, bo, j, lo, hi, ev, lav, dev, dur);
-                if (!MULTI) { la = lav; de = dev; }
-                else { sLa[j - a] = lav; sDe[j - a] = dev; }
+                sLa[j - a] = lav;
+                sDe[j - a] = dev;
                 backb[(size_t)i * p.bstride + j] = (unsigned short)dur;
                 if (p.log_alpha && j >= 1)
                     p.log_alpha[ro + (j - 1)] = (lav > MB_DEADF) ? lav * MB_LN2 : -__builtin_huge_valf();
                 if (i == I - 1 && j == J && p.map_score)
                     p.map_score[b] = (dev > MB_DEADF) ? dev * MB_LN2 : -__builtin_huge_valf();
-                if (!MULTI) break;
             }
         } else {
             // ---- no reachable position in this row: everything is "log 0" ----
-            la = MB_NEG;
-            de = MB_NEG;
 #pragma unroll 1
             for (int j = j1; j < bnd; j += T) {
-                if (MULTI) { sLa[j - a] = MB_NEG; sDe[j - a] = MB_NEG; }
+                sLa[j - a] = MB_NEG;
+                sDe[j - a] = MB_NEG;
                 if (p.log_alpha && j >= 1) p.log_alpha[ro + (j - 1)] = -__builtin_huge_valf();
                 if (i == I - 1 && j == J && p.map_score) p.map_score[b] = -__builtin_huge_valf();
             }
@@ -620,6 +627,16 @@ __device__ __forceinline__ void mb_window_fast(const float *__restrict__ sT, con
     }
 }
 
+// ... the FAST sum alone (the sum-product chain without the max-product one) ...
+__device__ __forceinline__ float mb_window_fast_sum(const float *__restrict__ t, int cnt) {
+    float acc = 0.f;
+    int c = 0;
+    for (const int r8 = cnt & 7; c < r8; ++c) acc += t[c];
+    for (; c < cnt; c += 8)
+        acc += ((t[c] + t[c + 1]) + (t[c + 2] + t[c + 3])) + ((t[c + 4] + t[c + 5]) + (t[c + 6] + t[c + 7]));
+    return acc;
+}
+
 // A wave's report about a row -- (a live exponent or MB_DEADM, "an entry does not fit") -- without atomics: every lane of the
 // wave stores the same pair into the wave's own slot (one ds_write_b64, no branch), and behind the row's barrier lane l of
 // every wave reads slot l & 15 and two ballots combine them.  Two slot sets by row parity; slots of waves that do not
@@ -655,8 +672,23 @@ __device__ __forceinline__ void mb_report_get(const int *sRep, int par, int lane
 // and every window's own largest term are normal floats of full precision, and a window is D additions.  Each wave
 // reports whether its entries fit (and their maximum, the next row's R); a row with an entry out of range takes
 // the exact sum, which needs no reference.
-template <int VT, bool WANT_LA, int H, bool STAMPS>
-__global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
+//
+// One body serves the three kernels below.  SUM: the sum-product chain runs (an entry is (M, s) and its fast term t; a
+// row stores log_alpha when WANT_LA).  MAP: the max-product chain runs (an entry is v; a row stores its durations, the
+// last row the score).  A chain that does not run leaves nothing behind: its LDS arrays, its ring planes, the waves'
+// reports (SUM only), its part of the window and its stores go at compile time, so each instantiation is still the
+// straight-line row described above.  The ring keeps one layout, [row][3][D] = planes M, s, v; a form publishes and
+// awaits the NPL planes of its chains and its ring pointers start at its first one.  What stays written per form is
+// the LDS write of phase 1 (the full kernel has no spare word in LDS for lanes without a position), the window, and
+// phase 1's arithmetic in the full kernel (measured: see there).
+template <int VT, int H, bool SUM, bool MAP, bool WANT_LA, bool STAMPS>
+__device__ __forceinline__ void mb_split_chain(MoboParams p) {
+    static_assert(SUM || MAP, "a chain must run");
+    static_assert(!STAMPS || (SUM && MAP), "the stamps belong to the full kernel");
+    constexpr bool LA = SUM && WANT_LA;
+    constexpr int NPL = (SUM ? 2 : 0) + (MAP ? 1 : 0);      // ring planes published and awaited
+    constexpr int VPL = NPL - 1;                            // v's plane, counted from the form's first
+    constexpr int NST = NPL + (MAP ? 1 : 0) + (LA ? 1 : 0);  // global stores of a row: the ring words, the duration, log_alpha
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // a launch that splits utterances (S > 1) carries one more wave: the HELPER takes the halo off the others' critical
     // path -- it fetches the previous segment's row, waits for it if it must, and puts it into LDS (550-850 of a row's
@@ -671,34 +703,31 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
 #define MB_STAMP(k_) if (stamping) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k_] += t_ - st_t; st_t = t_; }
     const int b = blockIdx.x / p.S, sg = blockIdx.x - b * p.S;
     const int D = p.D;
-    int I = p.t_xs[b], J = p.t_ys[b];
-    I = I > p.Tx ? p.Tx : I;
-    J = J > p.Ty ? p.Ty : J;
-    const bool ok = I >= 1 && J >= I && (long long)J <= (long long)I * D;
-    if (!ok) {
+    int I, J;
+    if (!mb_lengths(p.t_xs, p.t_ys, p.Tx, p.Ty, D, b, I, J)) {      // (both returns: whole workgroups, before any barrier)
         if (sg == 0 && tid == 0) atomicOr(p.status, ALIGNER_ST_BAD_LENGTHS);
         return;
     }
-    const int P = J + 1;
-    int Sb = P / D;
-    Sb = Sb < 1 ? 1 : (Sb > p.S ? p.S : Sb);
-    const int n = (P + Sb - 1) / Sb;
-    const int a = sg * n;
-    if (sg >= Sb || a >= P) return;
-    const int bnd = (a + n < P) ? a + n : P;
-    const bool has_next = (sg + 1 < Sb) && (a + n < P) && sg != p.drop_seg;
+    const MbGeom g = mb_segment(J, D, p.S, sg, p.drop_seg);
+    if (g.empty) return;
+    const int a = g.a, bnd = g.bnd;
+    const bool has_next = g.has_next;
     const int W = p.nmax + D;                      // entries per buffer
+    // LDS: [2][W] per array (row parity; D halo entries, then the segment's positions) -- M, s, (v,) t and the waves' reports
+    // [row parity][16 waves][2] (mb_report_put), or v alone; where the full kernel keeps v the sum-only one has room for a
+    // spare word, the map-only one after its one array: where lanes without a position write (never read)
     int *sM = reinterpret_cast<int *>(smem);
     float *sS = reinterpret_cast<float *>(sM + 2 * W);
-    float *sV = sS + 2 * W;
-    float *sT = sV + 2 * W;
-    int *sRep = reinterpret_cast<int *>(sT + 2 * W);    // [row parity][16 waves][2]: the waves' reports (mb_report_put)
-    if (tid < 32) { sRep[2 * tid] = MB_DEADM; sRep[2 * tid + 1] = 0; }
+    float *sV = SUM ? sS + 2 * W : reinterpret_cast<float *>(smem);
+    float *sT = (SUM && MAP) ? sV + 2 * W : sS + 2 * W;
+    int *sRep = reinterpret_cast<int *>(sT + 2 * W);
+    float *sSpare = SUM ? reinterpret_cast<float *>(sRep + 64) : sV + 2 * W;      // (not in the full kernel)
+    if (SUM && tid < 32) { sRep[2 * tid] = MB_DEADM; sRep[2 * tid + 1] = 0; }
     for (int h = tid; h < D; h += T) {             // positions before the utterance's start (segment 0 keeps these)
-        sM[h] = MB_DEADM;  sM[W + h] = MB_DEADM;
-        sS[h] = 0.f;       sS[W + h] = 0.f;
-        sV[h] = MB_NEG;    sV[W + h] = MB_NEG;
-        sT[h] = 0.f;       sT[W + h] = 0.f;
+        if (SUM) { sM[h] = MB_DEADM;  sM[W + h] = MB_DEADM; }
+        if (SUM) { sS[h] = 0.f;       sS[W + h] = 0.f; }
+        if (MAP) { sV[h] = MB_NEG;    sV[W + h] = MB_NEG; }
+        if (SUM) { sT[h] = 0.f;       sT[W + h] = 0.f; }
     }
     lds_barrier();
     const int pi = tid / H, sub = tid - pi * H;    // H consecutive lanes per position
@@ -709,8 +738,9 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     unsigned short *backb = p.back + (size_t)b * p.Tx * p.bstride;
     unsigned *trash = p.trash + (size_t)blockIdx.x * 1024 + tid;
-    unsigned *ring_out = p.ring + ((size_t)b * (p.S - 1) + (has_next ? sg : 0)) * (size_t)p.Tx * 3 * D;
-    const unsigned *ring_in = p.ring + ((size_t)b * (p.S - 1) + (sg > 0 ? sg - 1 : 0)) * (size_t)p.Tx * 3 * D;
+    constexpr int PL0 = SUM ? 0 : 2;               // the form's first ring plane
+    unsigned *ring_out = p.ring + ((size_t)b * (p.S - 1) + (has_next ? sg : 0)) * (size_t)p.Tx * 3 * D + PL0 * D;
+    const unsigned *ring_in = p.ring + ((size_t)b * (p.S - 1) + (sg > 0 ? sg - 1 : 0)) * (size_t)p.Tx * 3 * D + PL0 * D;
     const int hl = tid - T;                        // helper: its lane
     const bool publishes = has_next && lead && j1 >= bnd - D;
     // this lane's part of a window: entries [w0, w1) of its D
@@ -719,26 +749,29 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
     // rows [i0, i1]: the segment has a reachable position
     int i0, i1;
     mb_active_rows(I, J, D, a, bnd, i0, i1);
+    // an entry's ring words: (M, s) on the form's first two planes when SUM, v on its last when MAP
+    auto publish = [&](unsigned *r, int st, int M, float s, float v) {
+        if constexpr (SUM) {
+            mb_ring_store(r, __builtin_bit_cast(unsigned, (float)M));
+            mb_ring_store(r + st, __builtin_bit_cast(unsigned, s));
+        }
+        if constexpr (MAP) mb_ring_store(r + VPL * st, __builtin_bit_cast(unsigned, v));
+    };
     auto dead_rows = [&](int from, int to) {      // rows without a reachable position: "log 0" everywhere
         for (int i = from; i < to; ++i) {
             if (has_next && !helper)
-                for (int h = tid; h < D; h += T) {
-                    unsigned *r = ring_out + (size_t)i * 3 * D + h;
-                    mb_ring_store(r, __builtin_bit_cast(unsigned, (float)MB_DEADM));
-                    mb_ring_store(r + D, 0u);
-                    mb_ring_store(r + 2 * D, __builtin_bit_cast(unsigned, MB_NEG));
-                }
-            if (WANT_LA && lead && j1 >= 1) p.log_alpha[ubase + (size_t)i * p.Ty + (j1 - 1)] = -__builtin_huge_valf();
+                for (int h = tid; h < D; h += T) publish(ring_out + (size_t)i * 3 * D + h, D, MB_DEADM, 0.f, MB_NEG);
+            if (LA && lead && j1 >= 1) p.log_alpha[ubase + (size_t)i * p.Ty + (j1 - 1)] = -__builtin_huge_valf();
         }
     };
     if (i1 < 0) {                                  // never reachable (an utterance much shorter than the batch's Ty)
         dead_rows(0, I);
-        if (lead && j1 == J && p.map_score) p.map_score[b] = -__builtin_huge_valf();
+        if (MAP && lead && j1 == J && p.map_score) p.map_score[b] = -__builtin_huge_valf();
         return;
     }
     dead_rows(0, i0);
     bool gave_up = false;
-    int R = 0;                                     // the row's reference for the fast sum (uniform: every wave tracks it)
+    int R = 0;                                     // SUM: the row's reference for the fast sum (uniform: every wave tracks it)
     const int wave = tid >> 6, lane = tid & 63;
 
     if (helper) {
@@ -750,7 +783,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
                 // step pay a round trip to memory per row (measured: 1 200-3 000 cycles of every row).
                 int ig = i0 + p.start_lag;
                 ig = ig > I - 1 ? I - 1 : ig;
-                const unsigned *r = ring_in + (size_t)ig * 3 * D + (hl < D ? hl : 0) + 2 * D;    // the row's last word
+                const unsigned *r = ring_in + (size_t)ig * 3 * D + (hl < D ? hl : 0) + (NPL - 1) * D;    // the row's last word
                 int spins = 0;
                 while (mb_ring_load(r) == MB_FILL && !gave_up) {
                     __builtin_amdgcn_s_sleep(8);
@@ -758,63 +791,78 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
                 }
             }
             const bool fetches = hl < D;
-            unsigned h0_nx, h1_nx, h2_nx;
-            auto issue_halo = [&](int i) {
-                const unsigned *r = fetches ? ring_in + (size_t)i * 3 * D + hl : trash;
-                const int st = fetches ? D : 0;
-                h0_nx = mb_ring_load(r);
-                h1_nx = mb_ring_load(r + st);
-                h2_nx = mb_ring_load(r + 2 * st);
+            struct Words { unsigned w[NPL]; };           // an entry's ring words
+            auto load_words = [&](const unsigned *r, int st) {
+                Words x;
+#pragma unroll
+                for (int q = 0; q < NPL; ++q) x.w[q] = mb_ring_load(r + q * st);
+                return x;
             };
+            auto unpublished = [](const Words &x) {
+                bool u = false;
+#pragma unroll
+                for (int q = 0; q < NPL; ++q) u = u || x.w[q] == MB_FILL;
+                return u;
+            };
+            Words h_nx;
+            auto issue_halo = [&](int i) { h_nx = load_words(fetches ? ring_in + (size_t)i * 3 * D + hl : trash, fetches ? D : 0); };
             issue_halo(i0);
 #pragma unroll 1
             for (int i = i0; i <= i1; ++i) {
-                const unsigned h_c0 = h0_nx, h_c1 = h1_nx, h_c2 = h2_nx;
+                const Words h_c = h_nx;
                 issue_halo(i + 1 < I ? i + 1 : I - 1);
                 const int bo = (i & 1) * W;
                 // this lane's own entry comes from the words fetched a row ago: its test must not share a join with a
                 // path that loads (hipcc would then wait vmcnt(0) here -- for the loads issued a moment ago)
                 int Mstat = MB_DEADM;
                 bool fits = true;
-                auto halo_entry = [&](int h, unsigned x0, unsigned x1, unsigned x2) {
-                    if (x0 == MB_FILL || x1 == MB_FILL || x2 == MB_FILL) {          // not published yet: poll
+                auto halo_entry = [&](int h, Words x) {
+                    if (unpublished(x)) {                                           // not published yet: poll
                         const unsigned *r = ring_in + (size_t)i * 3 * D + h;
                         int spins = 0;
                         do {
                             __builtin_amdgcn_s_sleep(2);
-                            x0 = mb_ring_load(r);
-                            x1 = mb_ring_load(r + D);
-                            x2 = mb_ring_load(r + 2 * D);
+                            x = load_words(r, D);
                             if (++spins > p.spin_limit) gave_up = true;
-                        } while ((x0 == MB_FILL || x1 == MB_FILL || x2 == MB_FILL) && !gave_up);
+                        } while (unpublished(x) && !gave_up);
                     }
-                    const bool bad = (x0 == MB_FILL || x1 == MB_FILL || x2 == MB_FILL);
-                    const int M = bad ? MB_DEADM : (int)__builtin_bit_cast(float, x0);
-                    const float sv = bad ? 0.f : __builtin_bit_cast(float, x1);
-                    sM[bo + h] = M;
-                    sS[bo + h] = sv;
-                    sV[bo + h] = bad ? MB_NEG : __builtin_bit_cast(float, x2);
-                    sT[bo + h] = __builtin_ldexpf(sv, M - R);
-                    if (M != MB_DEADM) {
-                        Mstat = Mstat > M ? Mstat : M;
-                        fits = fits && M >= R - 100 && M <= R + 100;
+                    const bool bad = unpublished(x);
+                    const int M = (bad || !SUM) ? MB_DEADM : (int)__builtin_bit_cast(float, x.w[0]);
+                    const float sv = (bad || !SUM) ? 0.f : __builtin_bit_cast(float, x.w[SUM ? 1 : 0]);
+                    if constexpr (SUM) {
+                        sM[bo + h] = M;
+                        sS[bo + h] = sv;
+                    }
+                    if constexpr (MAP) sV[bo + h] = bad ? MB_NEG : __builtin_bit_cast(float, x.w[VPL]);
+                    if constexpr (SUM) {
+                        sT[bo + h] = __builtin_ldexpf(sv, M - R);
+                        if (M != MB_DEADM) {
+                            Mstat = Mstat > M ? Mstat : M;
+                            fits = fits && M >= R - 100 && M <= R + 100;
+                        }
                     }
                 };
-                if (fetches) halo_entry(hl, h_c0, h_c1, h_c2);
+                if (fetches) halo_entry(hl, h_c);
                 if (D > 64) {
+                    Words none;
+#pragma unroll
+                    for (int q = 0; q < NPL; ++q) none.w[q] = MB_FILL;
 #pragma unroll 1
-                    for (int h = hl + 64; h < D; h += 64) halo_entry(h, MB_FILL, MB_FILL, MB_FILL);
+                    for (int h = hl + 64; h < D; h += 64) halo_entry(h, none);
                 }
-                {   // the wave's report (mb_report_put: no atomics -- a same-address atomic per lane, or even per wave,
+                if constexpr (SUM) {
+                    // the wave's report (mb_report_put: no atomics -- a same-address atomic per lane, or even per wave,
                     // serialises in the LDS pipe and the barrier's lgkmcnt(0) waits for it)
                     const int wm = mb_wave_max_i32(Mstat);
                     const bool wfit = __builtin_amdgcn_ballot_w64(!fits) == 0;
                     mb_report_put(sRep, i & 1, wave, wm, wfit ? 0 : 1);
                 }
                 lds_barrier();
-                int Rn, slow_;
-                mb_report_get(sRep, i & 1, lane, Rn, slow_);
-                R = (Rn != MB_DEADM) ? Rn : R;
+                if constexpr (SUM) {
+                    int Rn, slow_;
+                    mb_report_get(sRep, i & 1, lane, Rn, slow_);
+                    R = (Rn != MB_DEADM) ? Rn : R;
+                }
             }
         }                                          // (segment 0 has no halo: the wave ends, a barrier only counts live waves)
         if (gave_up) {
@@ -840,24 +888,31 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
         L_o = p.Lw[ro + kl];
     };
     // without a helper wave (an unsplit launch) nobody else fetches a halo -- and there is none: S == 1
-    // The loop is entered in the state every later row finds: two rows of operand loads, each followed by a row's
-    // stores (three ring words, one duration, log_alpha).  hipcc sizes a counted wait for the FEWEST operations that can
+    // The loop is entered in the state every later row finds: two rows of operand loads, each followed by a row's NST
+    // stores (its ring words, a duration, log_alpha).  hipcc sizes a counted wait for the FEWEST operations that can
     // follow on any path into it: without these the waits inside the loop also waited for the previous row's stores to be
     // acknowledged -- 1 200 cycles of every row.
     issue(i0, e_n1, L_n1);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    if (WANT_LA) mb_ring_store(trash, 0u);
+#pragma unroll
+    for (int q = 0; q < NST; ++q) mb_ring_store(trash, 0u);
     issue(i0 + 1 < I ? i0 + 1 : I - 1, e_n2, L_n2);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    if (WANT_LA) mb_ring_store(trash, 0u);
+#pragma unroll
+    for (int q = 0; q < NST; ++q) mb_ring_store(trash, 0u);
     unsigned long long st_loop = 0;
     if (stamping) { st_loop = st_t = __builtin_amdgcn_s_memtime(); }
+    // this lane's entry of a row from its state of the row before: u = la - L as (M, s) when SUM, v = de - L when MAP
+    auto entry = [&](float Lraw, int &M, float &s, float &v) {
+        const float L = (j1 < J) ? Lraw : MB_NEG;     // the step out of J does not exist
+        const bool live = L > MB_DEADF;
+        M = MB_DEADM;
+        s = 0.f;
+        v = MB_NEG;
+        if constexpr (SUM) mb_encode((live && la > MB_DEADF) ? la - L : MB_NEG, M, s);
+        if constexpr (MAP) {
+            v = (live && de > MB_DEADF) ? de - L : MB_NEG;
+            v = (v > MB_DEADF) ? v : MB_NEG;
+        }
+    };
     auto do_row = [&](const int i, unsigned &e_s, float &L_s) {
         int lo, hi;
         mb_bounds(I, J, D, i, lo, hi);
@@ -870,35 +925,49 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
         MB_STAMP(0)
         // ---- phase 1: u = la_{i-1}(k) - L_i(k), v = delta_{i-1}(k) - L_i(k) ----
         {
-            const float L = (j1 < J) ? L_c : MB_NEG;
-            const bool live = L > MB_DEADF;
-            const float u = (live && la > MB_DEADF) ? la - L : MB_NEG;
-            float v = (live && de > MB_DEADF) ? de - L : MB_NEG;
-            v = (v > MB_DEADF) ? v : MB_NEG;
             int M;
-            float s;
-            mb_encode(u, M, s);
-            if (lead) {
-                const int x = bo + D + pi;
-                sM[x] = M;
-                sS[x] = s;
-                sV[x] = v;
-                sT[x] = __builtin_ldexpf(s, M - R);
+            float s, v;
+            if constexpr (SUM && MAP) {
+                // (per form: with entry() here the full kernel measured 3 % slower -- 687 against 667 us at D = 16,
+                // tools/experiments/mobo_full_kernel_entry_lambda.patch, profiles/mobo_split_chain_times.txt)
+                const float L = (j1 < J) ? L_c : MB_NEG;
+                const bool live = L > MB_DEADF;
+                const float u = (live && la > MB_DEADF) ? la - L : MB_NEG;
+                v = (live && de > MB_DEADF) ? de - L : MB_NEG;
+                v = (v > MB_DEADF) ? v : MB_NEG;
+                mb_encode(u, M, s);
+            } else {
+                entry(L_c, M, s, v);
             }
-            {   // the wave's report about the row -- one LDS atomic each: "an entry does not fit", and a candidate for the
-                // next row's reference: the M of ANY live lane will do (while the row fits, every live M is within 100 of
-                // R and so of one another; a wave-wide maximum costs six DPP steps a row)
+            // (per form: the full kernel's LDS has no spare word, so only a position's lead lane writes, under a branch; the
+            // short ones let every lane write, lanes without a position to the spare words -- one address select, no branch)
+            if constexpr (SUM && MAP) {
+                if (lead) {
+                    const int x = bo + D + pi;
+                    sM[x] = M;
+                    sS[x] = s;
+                    sV[x] = v;
+                    sT[x] = __builtin_ldexpf(s, M - R);
+                }
+            } else if constexpr (SUM) {
+                int *wm_ = mine ? sM + bo + D + pi : reinterpret_cast<int *>(sSpare);
+                wm_[0] = M;
+                reinterpret_cast<float *>(mine ? wm_ + 2 * W : wm_ + 1)[0] = s;
+                reinterpret_cast<float *>(mine ? wm_ + 4 * W : wm_ + 2)[0] = __builtin_ldexpf(s, M - R);
+            } else {
+                *(mine ? sV + bo + D + pi : sSpare) = v;
+            }
+            if constexpr (SUM) {
+                // the wave's report about the row -- "an entry does not fit", and a candidate for the next row's reference:
+                // the M of ANY live lane will do (while the row fits, every live M is within 100 of R and so of one
+                // another; a wave-wide maximum costs six DPP steps a row)
                 const bool livem = lead && M != MB_DEADM;
                 const unsigned long long lm = __builtin_amdgcn_ballot_w64(livem);
                 const bool wfit = __builtin_amdgcn_ballot_w64(livem && !(M >= R - 100 && M <= R + 100)) == 0;
                 const int wm = lm ? __builtin_amdgcn_readlane(M, __builtin_ctzll(lm)) : MB_DEADM;
                 mb_report_put(sRep, i & 1, wave, wm, wfit ? 0 : 1);
             }
-            unsigned *r = publishes ? ring_out + (size_t)i * 3 * D + (j1 - (bnd - D)) : trash;
-            const int st = publishes ? D : 0;
-            mb_ring_store(r, __builtin_bit_cast(unsigned, (float)M));
-            mb_ring_store(r + st, __builtin_bit_cast(unsigned, s));
-            mb_ring_store(r + 2 * st, __builtin_bit_cast(unsigned, v));
+            publish(publishes ? ring_out + (size_t)i * 3 * D + (j1 - (bnd - D)) : trash, publishes ? D : 0, M, s, v);
         }
         MB_STAMP(1)
         MB_STAMP(2)
@@ -906,16 +975,70 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
         MB_STAMP(3)
         // ---- phase 2: the windows [j-D, j) ----
         {
-            int Rn, slow;
-            mb_report_get(sRep, i & 1, lane, Rn, slow);
+            int Rn = MB_DEADM, slow = 0;
+            if constexpr (SUM) mb_report_get(sRep, i & 1, lane, Rn, slow);
             const float ev = mb_value<VT>(e_c) * MB_LOG2E;
             const bool feasible = mine && j1 >= lo && j1 <= hi;
             const int x = bo + (mine ? pi : 0) + w0;           // first entry of this lane's part
-            float lsum = MB_NEG, best;
-            int qb;
-            if (!slow) {
+            const int cnt = w1 - w0;
+            float lsum = MB_NEG, best = MB_NEG;
+            int qb = 0;
+            if constexpr (!SUM) {
+                // the maximum search alone: the largest v, among equals the largest index.  Written here, not as a function beside
+                // mb_window_fast: as one the map-only kernel measured 409 us against 389 at D = 16, the shape with eight
+                // entries a lane (tools/experiments/mobo_window_max_function.patch, profiles/mobo_split_chain_times.txt)
+                const float *vv = sV + x;
+                int c = 0;
+                for (const int r8 = cnt & 7; c < r8; ++c) {
+                    const float v = vv[c];
+                    if (v >= best) { best = v; qb = c; }
+                }
+                // (shallow trees: a lone wave per SIMD pays dependent latency -- the chunk's maximum by v_max3, then independent
+                // "equals the maximum ? index : -1" and an integer v_max3 tree for the LAST entry that has it; chains of
+                // 15 maxima and 15 selects measured 5 % slower at 16 entries a lane)
+#define MB_MAX3F(a_, b_, c_) __builtin_fmaxf(__builtin_fmaxf(a_, b_), c_)
+#define MB_MAX3I(a_, b_, c_) ((a_) > (b_) ? ((a_) > (c_) ? (a_) : (c_)) : ((b_) > (c_) ? (b_) : (c_)))
+                if (((cnt - c) & 15) == 0) {
+#pragma unroll 1
+                    for (; c < cnt; c += 16) {
+                        float v[16];
+#pragma unroll
+                        for (int u = 0; u < 16; ++u) v[u] = vv[c + u];
+                        const float m0 = MB_MAX3F(v[0], v[1], v[2]), m1 = MB_MAX3F(v[3], v[4], v[5]), m2 = MB_MAX3F(v[6], v[7], v[8]);
+                        const float m3 = MB_MAX3F(v[9], v[10], v[11]), m4 = MB_MAX3F(v[12], v[13], v[14]);
+                        const float vm = __builtin_fmaxf(MB_MAX3F(m0, m1, m2), MB_MAX3F(m3, m4, v[15]));
+                        int q[16];
+#pragma unroll
+                        for (int u = 0; u < 16; ++u) q[u] = (v[u] == vm) ? u : -1;
+                        const int q0 = MB_MAX3I(q[0], q[1], q[2]), q1 = MB_MAX3I(q[3], q[4], q[5]), q2 = MB_MAX3I(q[6], q[7], q[8]);
+                        const int q3 = MB_MAX3I(q[9], q[10], q[11]), q4 = MB_MAX3I(q[12], q[13], q[14]);
+                        const int qa = MB_MAX3I(q0, q1, q2), qc = MB_MAX3I(q3, q4, q[15]);
+                        const int qi = qa > qc ? qa : qc;
+                        const bool take = vm >= best;                           // (ties: the later chunk)
+                        best = take ? vm : best;
+                        qb = take ? c + qi : qb;
+                    }
+                } else {
+#pragma unroll 1
+                    for (; c < cnt; c += 8) {
+                        float v[8];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) v[u] = vv[c + u];
+                        float vm = v[0];                                        // (at eight entries the plain chains are the faster form)
+#pragma unroll
+                        for (int u = 1; u < 8; ++u) vm = __builtin_fmaxf(vm, v[u]);
+                        int qi = 0;
+#pragma unroll
+                        for (int u = 1; u < 8; ++u) qi = (v[u] == vm) ? u : qi;
+                        if (vm >= best) { best = vm; qb = c + qi; }
+                    }
+                }
+#undef MB_MAX3F
+#undef MB_MAX3I
+            } else if (!slow) {
                 float acc;
-                mb_window_fast(sT + x, sV + x, w1 - w0, acc, best, qb);
+                if constexpr (MAP) mb_window_fast(sT + x, sV + x, cnt, acc, best, qb);
+                else acc = mb_window_fast_sum(sT + x, cnt);
 #pragma unroll
                 for (int m = 1; m < H; m <<= 1) acc += mb_quad_xor_f(acc, m);
                 if (acc > 0.f) lsum = (float)R + __builtin_amdgcn_logf(acc);
@@ -923,7 +1046,7 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
                 if (stamping) ++st_slow;
                 int Mw;
                 float acc;
-                mb_window<true>(sM + x, sS + x, sV + x, w1 - w0, Mw, acc, best, qb);
+                mb_window<MAP>(sM + x, sS + x, MAP ? sV + x : nullptr, cnt, Mw, acc, best, qb);
 #pragma unroll
                 for (int m = 1; m < H; m <<= 1) {
                     const int Mo = mb_quad_xor_i(Mw, m);
@@ -934,32 +1057,36 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
                 }
                 if (acc > 0.f) lsum = (float)Mw + __builtin_amdgcn_logf(acc);
             }
-            qb += w0;
+            if constexpr (MAP) {
+                qb += w0;
 #pragma unroll
-            for (int m = 1; m < H; m <<= 1) {                  // the largest v; among equals the largest index
-                const float bo_ = mb_quad_xor_f(best, m);
-                const int qo = mb_quad_xor_i(qb, m);
-                const bool take = bo_ > best || (bo_ == best && qo > qb);
-                best = take ? bo_ : best;
-                qb = take ? qo : qb;
+                for (int m = 1; m < H; m <<= 1) {              // the largest v; among equals the largest index
+                    const float bo_ = mb_quad_xor_f(best, m);
+                    const int qo = mb_quad_xor_i(qb, m);
+                    const bool take = bo_ > best || (bo_ == best && qo > qb);
+                    best = take ? bo_ : best;
+                    qb = take ? qo : qb;
+                }
             }
             float lav = MB_NEG, dev = MB_NEG;
             int dur = 0;
             if (feasible && ev > MB_DEADF) {
-                if (lsum > MB_DEADF) lav = ev + lsum;
-                if (best > MB_DEADF) { dev = ev + best; dur = D - qb; }
+                if (SUM && lsum > MB_DEADF) lav = ev + lsum;
+                if (MAP && best > MB_DEADF) { dev = ev + best; dur = D - qb; }
                 lav = (lav > MB_DEADF) ? lav : MB_NEG;
                 dev = (dev > MB_DEADF) ? dev : MB_NEG;
                 if (!(dev > MB_DEADF)) dur = 0;
             }
             la = lav;
             de = dev;
-            R = (Rn != MB_DEADM) ? Rn : R;
+            if constexpr (SUM) R = (Rn != MB_DEADM) ? Rn : R;
             if (stamping) { asm volatile("" :: "v"(la), "v"(de)); }
             MB_STAMP(4)
-            unsigned short *bp = lead ? backb + (size_t)i * p.bstride + j1 : reinterpret_cast<unsigned short *>(trash);
-            *bp = (unsigned short)dur;
-            if (WANT_LA) {
+            if constexpr (MAP) {
+                unsigned short *bp = lead ? backb + (size_t)i * p.bstride + j1 : reinterpret_cast<unsigned short *>(trash);
+                *bp = (unsigned short)dur;
+            }
+            if constexpr (LA) {
                 float *lp = (lead && j1 >= 1) ? p.log_alpha + ro + (j1 - 1) : reinterpret_cast<float *>(trash);
                 *lp = (lav > MB_DEADF) ? lav * MB_LN2 : -__builtin_huge_valf();
             }
@@ -981,534 +1108,42 @@ __global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
         o[15] = st_acc[6]; o[16] = st_acc[7]; o[17] = st_acc[8];
     }
 #undef MB_STAMP
-    if (lead && j1 == J && i1 == I - 1 && p.map_score)
+    if (MAP && lead && j1 == J && i1 == I - 1 && p.map_score)
         p.map_score[b] = (de > MB_DEADF) ? de * MB_LN2 : -__builtin_huge_valf();
     if (i1 + 1 < I) {
         // row i1+1: nothing reachable here any more, but the states of row i1 are still owed to the next segment
         const int i = i1 + 1;
         if (publishes) {
-            const float Lr = p.Lw[ubase + (size_t)i * p.Ty + kl];
-            const float L = (j1 < J) ? Lr : MB_NEG;
-            const bool live = L > MB_DEADF;
-            const float u = (live && la > MB_DEADF) ? la - L : MB_NEG;
-            float v = (live && de > MB_DEADF) ? de - L : MB_NEG;
-            v = (v > MB_DEADF) ? v : MB_NEG;
             int M;
-            float s;
-            mb_encode(u, M, s);
-            unsigned *r = ring_out + (size_t)i * 3 * D + (j1 - (bnd - D));
-            mb_ring_store(r, __builtin_bit_cast(unsigned, (float)M));
-            mb_ring_store(r + D, __builtin_bit_cast(unsigned, s));
-            mb_ring_store(r + 2 * D, __builtin_bit_cast(unsigned, v));
+            float s, v;
+            entry(p.Lw[ubase + (size_t)i * p.Ty + kl], M, s, v);
+            publish(ring_out + (size_t)i * 3 * D + (j1 - (bnd - D)), D, M, s, v);
         }
-        if (WANT_LA && lead && j1 >= 1) p.log_alpha[ubase + (size_t)i * p.Ty + (j1 - 1)] = -__builtin_huge_valf();
+        if (LA && lead && j1 >= 1) p.log_alpha[ubase + (size_t)i * p.Ty + (j1 - 1)] = -__builtin_huge_valf();
         dead_rows(i1 + 2, I);
-        if (lead && j1 == J && p.map_score) p.map_score[b] = -__builtin_huge_valf();
+        if (MAP && lead && j1 == J && p.map_score) p.map_score[b] = -__builtin_huge_valf();
     }
 }
 
-// The split form when only the MAP sequence is asked for (no log_alpha): the max-product chain alone.  It never reads the
-// sum-product one, so everything that serves the sums goes -- the (M, s) encoding, the fast terms and their reference,
-// the waves' reports, the exact sums, two of the three ring words, the window's additions and its logarithm: a row is a
-// subtraction, one LDS write, one ring word, a barrier, the window's maximum with its position, an addition.  Same
-// devices otherwise (helper wave, operands two rows ahead, counted waits, trash-address stores), same results bit for
-// bit (`mobo_full_chain` selects the full kernel for the comparison: tests/test_mobo.py).
+// Both chains: log_alpha (WANT_LA) and the MAP sequence.
+template <int VT, bool WANT_LA, int H, bool STAMPS>
+__global__ __launch_bounds__(1024) void mobo_chain_one_kernel(MoboParams p) {
+    mb_split_chain<VT, H, true, true, WANT_LA, STAMPS>(p);
+}
+
+// Only the MAP sequence is asked for (no log_alpha): the max-product chain alone.  It never reads the sum-product one, so
+// a row is a subtraction, one LDS write, one ring word, a barrier, the window's maximum with its position, an addition.
+// Same results bit for bit (`mobo_full_chain` selects the full kernel for the comparison: tests/test_mobo.py).
 template <int VT, int H>
 __global__ __launch_bounds__(1024) void mobo_chain_map_kernel(MoboParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const bool has_helper = p.S > 1;
-    const int T = (int)blockDim.x - (has_helper ? 64 : 0);
-    const bool helper = tid >= T;
-    const int b = blockIdx.x / p.S, sg = blockIdx.x - b * p.S;
-    const int D = p.D;
-    int I = p.t_xs[b], J = p.t_ys[b];
-    I = I > p.Tx ? p.Tx : I;
-    J = J > p.Ty ? p.Ty : J;
-    const bool ok = I >= 1 && J >= I && (long long)J <= (long long)I * D;
-    if (!ok) {
-        if (sg == 0 && tid == 0) atomicOr(p.status, ALIGNER_ST_BAD_LENGTHS);
-        return;
-    }
-    const int P = J + 1;
-    int Sb = P / D;
-    Sb = Sb < 1 ? 1 : (Sb > p.S ? p.S : Sb);
-    const int n = (P + Sb - 1) / Sb;
-    const int a = sg * n;
-    if (sg >= Sb || a >= P) return;
-    const int bnd = (a + n < P) ? a + n : P;
-    const bool has_next = (sg + 1 < Sb) && (a + n < P) && sg != p.drop_seg;
-    const int W = p.nmax + D;
-    float *sV = reinterpret_cast<float *>(smem);          // [2][W]: D halo entries, then the segment's positions
-    float *sSpare = sV + 2 * W;                           // where lanes without a position write (never read)
-    for (int h = tid; h < D; h += T) {                    // positions before the utterance's start (segment 0 keeps these)
-        sV[h] = MB_NEG;
-        sV[W + h] = MB_NEG;
-    }
-    lds_barrier();
-    const int pi = tid / H, sub = tid - pi * H;
-    const int j1 = a + pi;
-    const bool mine = !helper && j1 < bnd;
-    const bool lead = mine && sub == 0;
-    float de = (j1 == 0) ? 0.f : MB_NEG;                  // P(b_-1 = 0) = 1
-    const size_t ubase = (size_t)b * p.Tx * p.Ty;
-    unsigned short *backb = p.back + (size_t)b * p.Tx * p.bstride;
-    unsigned *trash = p.trash + (size_t)blockIdx.x * 1024 + tid;
-    // (the ring keeps the full kernel's layout [row][3][D]; only its third plane, v, is written and awaited)
-    unsigned *ring_out = p.ring + ((size_t)b * (p.S - 1) + (has_next ? sg : 0)) * (size_t)p.Tx * 3 * D + 2 * D;
-    const unsigned *ring_in = p.ring + ((size_t)b * (p.S - 1) + (sg > 0 ? sg - 1 : 0)) * (size_t)p.Tx * 3 * D + 2 * D;
-    const int hl = tid - T;
-    const bool publishes = has_next && lead && j1 >= bnd - D;
-    const int w0 = (sub * D) / H, w1 = ((sub + 1) * D) / H;
-    int i0, i1;
-    mb_active_rows(I, J, D, a, bnd, i0, i1);
-    auto dead_rows = [&](int from, int to) {
-        if (has_next && !helper)
-            for (int i = from; i < to; ++i)
-                for (int h = tid; h < D; h += T) mb_ring_store(ring_out + (size_t)i * 3 * D + h, __builtin_bit_cast(unsigned, MB_NEG));
-    };
-    if (i1 < 0) {
-        dead_rows(0, I);
-        if (lead && j1 == J && p.map_score) p.map_score[b] = -__builtin_huge_valf();
-        return;
-    }
-    dead_rows(0, i0);
-    bool gave_up = false;
-
-    if (helper) {
-        if (sg > 0) {
-            if (p.start_lag > 0) {
-                int ig = i0 + p.start_lag;
-                ig = ig > I - 1 ? I - 1 : ig;
-                const unsigned *r = ring_in + (size_t)ig * 3 * D + (hl < D ? hl : 0);
-                int spins = 0;
-                while (mb_ring_load(r) == MB_FILL && !gave_up) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > p.spin_limit) gave_up = true;
-                }
-            }
-            const bool fetches = hl < D;
-            unsigned h_nx;
-            auto issue_halo = [&](int i) { h_nx = mb_ring_load(fetches ? ring_in + (size_t)i * 3 * D + hl : trash); };
-            issue_halo(i0);
-#pragma unroll 1
-            for (int i = i0; i <= i1; ++i) {
-                const unsigned h_c = h_nx;
-                issue_halo(i + 1 < I ? i + 1 : I - 1);
-                const int bo = (i & 1) * W;
-                auto halo_entry = [&](int h, unsigned x) {
-                    if (x == MB_FILL) {                                            // not published yet: poll
-                        const unsigned *r = ring_in + (size_t)i * 3 * D + h;
-                        int spins = 0;
-                        do {
-                            __builtin_amdgcn_s_sleep(2);
-                            x = mb_ring_load(r);
-                            if (++spins > p.spin_limit) gave_up = true;
-                        } while (x == MB_FILL && !gave_up);
-                    }
-                    sV[bo + h] = (x == MB_FILL) ? MB_NEG : __builtin_bit_cast(float, x);
-                };
-                if (fetches) halo_entry(hl, h_c);
-                if (D > 64) {
-#pragma unroll 1
-                    for (int h = hl + 64; h < D; h += 64) halo_entry(h, MB_FILL);
-                }
-                lds_barrier();
-            }
-        }
-        if (gave_up) {
-            atomicOr(p.status, ALIGNER_ST_INTERNAL);
-            p.failw[b] = 1;
-        }
-        return;
-    }
-
-    const int je = (j1 < 1 ? 1 : (j1 > J ? J : j1)) - 1;
-    const int kl = j1 > J - 1 ? J - 1 : j1;
-    unsigned e_n1, e_n2;
-    float L_n1, L_n2;
-    auto issue = [&](int i, unsigned &e_o, float &L_o) {
-        const size_t ro = ubase + (size_t)i * p.Ty;
-        e_o = mb_load_raw<VT>(p.e, ro + je);
-        L_o = p.Lw[ro + kl];
-    };
-    // (entered in the state every later row finds: two rows of operand loads, each with a row's two stores behind it)
-    issue(i0, e_n1, L_n1);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    issue(i0 + 1 < I ? i0 + 1 : I - 1, e_n2, L_n2);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    auto do_row = [&](const int i, unsigned &e_s, float &L_s) {
-        int lo, hi;
-        mb_bounds(I, J, D, i, lo, hi);
-        const unsigned e_c = e_s;
-        const float L_c = L_s;
-        issue(i + 2 < I ? i + 2 : I - 1, e_s, L_s);
-        const int bo = (i & 1) * W;
-        {   // phase 1: v = delta_{i-1}(k) - L_i(k)
-            const float L = (j1 < J) ? L_c : MB_NEG;
-            float v = (L > MB_DEADF && de > MB_DEADF) ? de - L : MB_NEG;
-            v = (v > MB_DEADF) ? v : MB_NEG;
-            *(mine ? sV + bo + D + pi : sSpare) = v;
-            mb_ring_store(publishes ? ring_out + (size_t)i * 3 * D + (j1 - (bnd - D)) : trash, __builtin_bit_cast(unsigned, v));
-        }
-        lds_barrier();
-        {   // phase 2: the window [j-D, j): its largest v, among equals the largest index
-            const float ev = mb_value<VT>(e_c) * MB_LOG2E;
-            const bool feasible = mine && j1 >= lo && j1 <= hi;
-            const float *vv = sV + bo + (mine ? pi : 0) + w0;
-            const int cnt = w1 - w0;
-            float best = MB_NEG;
-            int qb = 0, c = 0;
-            for (const int r8 = cnt & 7; c < r8; ++c) {
-                const float v = vv[c];
-                if (v >= best) { best = v; qb = c; }
-            }
-            // (shallow trees: a lone wave per SIMD pays dependent latency -- the chunk's maximum by v_max3, then independent
-            // "equals the maximum ? index : -1" and an integer v_max3 tree for the LAST entry that has it; chains of
-            // 15 maxima and 15 selects measured 5 % slower at 16 entries a lane)
-#define MB_MAX3F(a_, b_, c_) __builtin_fmaxf(__builtin_fmaxf(a_, b_), c_)
-#define MB_MAX3I(a_, b_, c_) ((a_) > (b_) ? ((a_) > (c_) ? (a_) : (c_)) : ((b_) > (c_) ? (b_) : (c_)))
-            if (((cnt - c) & 15) == 0) {
-#pragma unroll 1
-                for (; c < cnt; c += 16) {
-                    float v[16];
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) v[u] = vv[c + u];
-                    const float m0 = MB_MAX3F(v[0], v[1], v[2]), m1 = MB_MAX3F(v[3], v[4], v[5]), m2 = MB_MAX3F(v[6], v[7], v[8]);
-                    const float m3 = MB_MAX3F(v[9], v[10], v[11]), m4 = MB_MAX3F(v[12], v[13], v[14]);
-                    const float vm = __builtin_fmaxf(MB_MAX3F(m0, m1, m2), MB_MAX3F(m3, m4, v[15]));
-                    int q[16];
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) q[u] = (v[u] == vm) ? u : -1;
-                    const int q0 = MB_MAX3I(q[0], q[1], q[2]), q1 = MB_MAX3I(q[3], q[4], q[5]), q2 = MB_MAX3I(q[6], q[7], q[8]);
-                    const int q3 = MB_MAX3I(q[9], q[10], q[11]), q4 = MB_MAX3I(q[12], q[13], q[14]);
-                    const int qa = MB_MAX3I(q0, q1, q2), qc = MB_MAX3I(q3, q4, q[15]);
-                    const int qi = qa > qc ? qa : qc;
-                    const bool take = vm >= best;                               // (ties: the later chunk)
-                    best = take ? vm : best;
-                    qb = take ? c + qi : qb;
-                }
-            } else {
-#pragma unroll 1
-                for (; c < cnt; c += 8) {
-                    float v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = vv[c + u];
-                    float vm = v[0];                                            // (at eight entries the plain chains are the faster form)
-#pragma unroll
-                    for (int u = 1; u < 8; ++u) vm = __builtin_fmaxf(vm, v[u]);
-                    int qi = 0;
-#pragma unroll
-                    for (int u = 1; u < 8; ++u) qi = (v[u] == vm) ? u : qi;
-                    if (vm >= best) { best = vm; qb = c + qi; }
-                }
-            }
-#undef MB_MAX3F
-#undef MB_MAX3I
-            qb += w0;
-#pragma unroll
-            for (int m = 1; m < H; m <<= 1) {
-                const float bo_ = mb_quad_xor_f(best, m);
-                const int qo = mb_quad_xor_i(qb, m);
-                const bool take = bo_ > best || (bo_ == best && qo > qb);
-                best = take ? bo_ : best;
-                qb = take ? qo : qb;
-            }
-            float dev = MB_NEG;
-            int dur = 0;
-            if (feasible && ev > MB_DEADF && best > MB_DEADF) {
-                dev = ev + best;
-                dur = D - qb;
-                if (!(dev > MB_DEADF)) { dev = MB_NEG; dur = 0; }
-            }
-            de = dev;
-            unsigned short *bp = lead ? backb + (size_t)i * p.bstride + j1 : reinterpret_cast<unsigned short *>(trash);
-            *bp = (unsigned short)dur;
-        }
-    };
-#pragma unroll 1
-    for (int i = i0; i <= i1; i += 2) {
-        do_row(i, e_n1, L_n1);
-        if (i + 1 > i1) break;
-        do_row(i + 1, e_n2, L_n2);
-    }
-    if (lead && j1 == J && i1 == I - 1 && p.map_score)
-        p.map_score[b] = (de > MB_DEADF) ? de * MB_LN2 : -__builtin_huge_valf();
-    if (i1 + 1 < I) {
-        // row i1+1: nothing reachable here any more, but the states of row i1 are still owed to the next segment
-        const int i = i1 + 1;
-        if (publishes) {
-            const float Lr = p.Lw[ubase + (size_t)i * p.Ty + kl];
-            const float L = (j1 < J) ? Lr : MB_NEG;
-            float v = (L > MB_DEADF && de > MB_DEADF) ? de - L : MB_NEG;
-            v = (v > MB_DEADF) ? v : MB_NEG;
-            mb_ring_store(ring_out + (size_t)i * 3 * D + (j1 - (bnd - D)), __builtin_bit_cast(unsigned, v));
-        }
-        dead_rows(i1 + 2, I);
-        if (lead && j1 == J && p.map_score) p.map_score[b] = -__builtin_huge_valf();
-    }
+    mb_split_chain<VT, H, false, true, false, false>(p);
 }
 
-// ... and the split form when only log_alpha (and gamma) is asked for -- a training step's forward pass: the sum-product
-// chain alone.  No v, no maximum and position, no durations plane, one ring word less; the window is its fast terms'
-// sum (or the exact (M, s) sum in a row that does not fit).  Bit for bit the full kernel's log_alpha.
+// Only log_alpha (and gamma) is asked for -- a training step's forward pass: the sum-product chain alone.  The window is
+// its fast terms' sum (or the exact (M, s) sum in a row that does not fit).  Bit for bit the full kernel's log_alpha.
 template <int VT, int H>
 __global__ __launch_bounds__(1024) void mobo_chain_sum_kernel(MoboParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const bool has_helper = p.S > 1;
-    const int T = (int)blockDim.x - (has_helper ? 64 : 0);
-    const bool helper = tid >= T;
-    const int b = blockIdx.x / p.S, sg = blockIdx.x - b * p.S;
-    const int D = p.D;
-    int I = p.t_xs[b], J = p.t_ys[b];
-    I = I > p.Tx ? p.Tx : I;
-    J = J > p.Ty ? p.Ty : J;
-    const bool ok = I >= 1 && J >= I && (long long)J <= (long long)I * D;
-    if (!ok) {
-        if (sg == 0 && tid == 0) atomicOr(p.status, ALIGNER_ST_BAD_LENGTHS);
-        return;
-    }
-    const int P = J + 1;
-    int Sb = P / D;
-    Sb = Sb < 1 ? 1 : (Sb > p.S ? p.S : Sb);
-    const int n = (P + Sb - 1) / Sb;
-    const int a = sg * n;
-    if (sg >= Sb || a >= P) return;
-    const int bnd = (a + n < P) ? a + n : P;
-    const bool has_next = (sg + 1 < Sb) && (a + n < P) && sg != p.drop_seg;
-    const int W = p.nmax + D;
-    int *sM = reinterpret_cast<int *>(smem);
-    float *sS = reinterpret_cast<float *>(sM + 2 * W);
-    float *sT = sS + 2 * W;
-    int *sRep = reinterpret_cast<int *>(sT + 2 * W);      // (the full kernel's fourth array is free here: room for both)
-    float *sSpare = reinterpret_cast<float *>(sRep + 64);
-    if (tid < 32) { sRep[2 * tid] = MB_DEADM; sRep[2 * tid + 1] = 0; }
-    for (int h = tid; h < D; h += T) {
-        sM[h] = MB_DEADM;  sM[W + h] = MB_DEADM;
-        sS[h] = 0.f;       sS[W + h] = 0.f;
-        sT[h] = 0.f;       sT[W + h] = 0.f;
-    }
-    lds_barrier();
-    const int pi = tid / H, sub = tid - pi * H;
-    const int j1 = a + pi;
-    const bool mine = !helper && j1 < bnd;
-    const bool lead = mine && sub == 0;
-    float la = (j1 == 0) ? 0.f : MB_NEG;
-    const size_t ubase = (size_t)b * p.Tx * p.Ty;
-    unsigned *trash = p.trash + (size_t)blockIdx.x * 1024 + tid;
-    unsigned *ring_out = p.ring + ((size_t)b * (p.S - 1) + (has_next ? sg : 0)) * (size_t)p.Tx * 3 * D;
-    const unsigned *ring_in = p.ring + ((size_t)b * (p.S - 1) + (sg > 0 ? sg - 1 : 0)) * (size_t)p.Tx * 3 * D;
-    const int hl = tid - T;
-    const bool publishes = has_next && lead && j1 >= bnd - D;
-    const int w0 = (sub * D) / H, w1 = ((sub + 1) * D) / H;
-    const int wave = tid >> 6, lane = tid & 63;
-    int i0, i1;
-    mb_active_rows(I, J, D, a, bnd, i0, i1);
-    auto dead_rows = [&](int from, int to) {
-        for (int i = from; i < to; ++i) {
-            if (has_next && !helper)
-                for (int h = tid; h < D; h += T) {
-                    unsigned *r = ring_out + (size_t)i * 3 * D + h;
-                    mb_ring_store(r, __builtin_bit_cast(unsigned, (float)MB_DEADM));
-                    mb_ring_store(r + D, 0u);
-                }
-            if (lead && j1 >= 1) p.log_alpha[ubase + (size_t)i * p.Ty + (j1 - 1)] = -__builtin_huge_valf();
-        }
-    };
-    if (i1 < 0) {
-        dead_rows(0, I);
-        return;
-    }
-    dead_rows(0, i0);
-    bool gave_up = false;
-    int R = 0;
-
-    if (helper) {
-        if (sg > 0) {
-            if (p.start_lag > 0) {
-                int ig = i0 + p.start_lag;
-                ig = ig > I - 1 ? I - 1 : ig;
-                const unsigned *r = ring_in + (size_t)ig * 3 * D + (hl < D ? hl : 0) + D;        // the row's last word
-                int spins = 0;
-                while (mb_ring_load(r) == MB_FILL && !gave_up) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > p.spin_limit) gave_up = true;
-                }
-            }
-            const bool fetches = hl < D;
-            unsigned h0_nx, h1_nx;
-            auto issue_halo = [&](int i) {
-                const unsigned *r = fetches ? ring_in + (size_t)i * 3 * D + hl : trash;
-                h0_nx = mb_ring_load(r);
-                h1_nx = mb_ring_load(r + (fetches ? D : 0));
-            };
-            issue_halo(i0);
-#pragma unroll 1
-            for (int i = i0; i <= i1; ++i) {
-                const unsigned h_c0 = h0_nx, h_c1 = h1_nx;
-                issue_halo(i + 1 < I ? i + 1 : I - 1);
-                const int bo = (i & 1) * W;
-                int Mstat = MB_DEADM;
-                bool fits = true;
-                auto halo_entry = [&](int h, unsigned x0, unsigned x1) {
-                    if (x0 == MB_FILL || x1 == MB_FILL) {
-                        const unsigned *r = ring_in + (size_t)i * 3 * D + h;
-                        int spins = 0;
-                        do {
-                            __builtin_amdgcn_s_sleep(2);
-                            x0 = mb_ring_load(r);
-                            x1 = mb_ring_load(r + D);
-                            if (++spins > p.spin_limit) gave_up = true;
-                        } while ((x0 == MB_FILL || x1 == MB_FILL) && !gave_up);
-                    }
-                    const bool bad = (x0 == MB_FILL || x1 == MB_FILL);
-                    const int M = bad ? MB_DEADM : (int)__builtin_bit_cast(float, x0);
-                    const float sv = bad ? 0.f : __builtin_bit_cast(float, x1);
-                    sM[bo + h] = M;
-                    sS[bo + h] = sv;
-                    sT[bo + h] = __builtin_ldexpf(sv, M - R);
-                    if (M != MB_DEADM) {
-                        Mstat = Mstat > M ? Mstat : M;
-                        fits = fits && M >= R - 100 && M <= R + 100;
-                    }
-                };
-                if (fetches) halo_entry(hl, h_c0, h_c1);
-                if (D > 64) {
-#pragma unroll 1
-                    for (int h = hl + 64; h < D; h += 64) halo_entry(h, MB_FILL, MB_FILL);
-                }
-                {
-                    const int wm = mb_wave_max_i32(Mstat);
-                    const bool wfit = __builtin_amdgcn_ballot_w64(!fits) == 0;
-                    mb_report_put(sRep, i & 1, wave, wm, wfit ? 0 : 1);
-                }
-                lds_barrier();
-                int Rn, slow_;
-                mb_report_get(sRep, i & 1, lane, Rn, slow_);
-                R = (Rn != MB_DEADM) ? Rn : R;
-            }
-        }
-        if (gave_up) {
-            atomicOr(p.status, ALIGNER_ST_INTERNAL);
-            p.failw[b] = 1;
-        }
-        return;
-    }
-
-    const int je = (j1 < 1 ? 1 : (j1 > J ? J : j1)) - 1;
-    const int kl = j1 > J - 1 ? J - 1 : j1;
-    unsigned e_n1, e_n2;
-    float L_n1, L_n2;
-    auto issue = [&](int i, unsigned &e_o, float &L_o) {
-        const size_t ro = ubase + (size_t)i * p.Ty;
-        e_o = mb_load_raw<VT>(p.e, ro + je);
-        L_o = p.Lw[ro + kl];
-    };
-    // (entered in the state every later row finds: two rows of operand loads, each with a row's three stores behind it)
-    issue(i0, e_n1, L_n1);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    issue(i0 + 1 < I ? i0 + 1 : I - 1, e_n2, L_n2);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    mb_ring_store(trash, 0u);
-    auto do_row = [&](const int i, unsigned &e_s, float &L_s) {
-        int lo, hi;
-        mb_bounds(I, J, D, i, lo, hi);
-        const unsigned e_c = e_s;
-        const float L_c = L_s;
-        issue(i + 2 < I ? i + 2 : I - 1, e_s, L_s);
-        const size_t ro = ubase + (size_t)i * p.Ty;
-        const int bo = (i & 1) * W;
-        {   // phase 1: u = la_{i-1}(k) - L_i(k)
-            const float L = (j1 < J) ? L_c : MB_NEG;
-            const float u = (L > MB_DEADF && la > MB_DEADF) ? la - L : MB_NEG;
-            int M;
-            float sm;
-            mb_encode(u, M, sm);
-            int *wm_ = mine ? sM + bo + D + pi : reinterpret_cast<int *>(sSpare);
-            wm_[0] = M;
-            reinterpret_cast<float *>(mine ? wm_ + 2 * W : wm_ + 1)[0] = sm;
-            reinterpret_cast<float *>(mine ? wm_ + 4 * W : wm_ + 2)[0] = __builtin_ldexpf(sm, M - R);
-            {
-                const bool livem = lead && M != MB_DEADM;
-                const unsigned long long lm = __builtin_amdgcn_ballot_w64(livem);
-                const bool wfit = __builtin_amdgcn_ballot_w64(livem && !(M >= R - 100 && M <= R + 100)) == 0;
-                const int wm = lm ? __builtin_amdgcn_readlane(M, __builtin_ctzll(lm)) : MB_DEADM;
-                mb_report_put(sRep, i & 1, wave, wm, wfit ? 0 : 1);
-            }
-            unsigned *r = publishes ? ring_out + (size_t)i * 3 * D + (j1 - (bnd - D)) : trash;
-            mb_ring_store(r, __builtin_bit_cast(unsigned, (float)M));
-            mb_ring_store(r + (publishes ? D : 0), __builtin_bit_cast(unsigned, sm));
-        }
-        lds_barrier();
-        {   // phase 2: the window [j-D, j)
-            int Rn, slow;
-            mb_report_get(sRep, i & 1, lane, Rn, slow);
-            const float ev = mb_value<VT>(e_c) * MB_LOG2E;
-            const bool feasible = mine && j1 >= lo && j1 <= hi;
-            const int x = bo + (mine ? pi : 0) + w0;
-            const int cnt = w1 - w0;
-            float lsum = MB_NEG;
-            if (!slow) {
-                const float *t = sT + x;
-                float acc = 0.f;
-                int c = 0;
-                for (const int r8 = cnt & 7; c < r8; ++c) acc += t[c];
-                for (; c < cnt; c += 8)
-                    acc += ((t[c] + t[c + 1]) + (t[c + 2] + t[c + 3])) + ((t[c + 4] + t[c + 5]) + (t[c + 6] + t[c + 7]));
-#pragma unroll
-                for (int m = 1; m < H; m <<= 1) acc += mb_quad_xor_f(acc, m);
-                if (acc > 0.f) lsum = (float)R + __builtin_amdgcn_logf(acc);
-            } else {
-                int Mw, qb;
-                float acc, best;
-                mb_window<false>(sM + x, sS + x, nullptr, cnt, Mw, acc, best, qb);
-#pragma unroll
-                for (int m = 1; m < H; m <<= 1) {
-                    const int Mo = mb_quad_xor_i(Mw, m);
-                    const float ao = mb_quad_xor_f(acc, m);
-                    const int Mn = Mw > Mo ? Mw : Mo;
-                    acc = __builtin_ldexpf(acc, Mw - Mn) + __builtin_ldexpf(ao, Mo - Mn);
-                    Mw = Mn;
-                }
-                if (acc > 0.f) lsum = (float)Mw + __builtin_amdgcn_logf(acc);
-            }
-            float lav = MB_NEG;
-            if (feasible && ev > MB_DEADF && lsum > MB_DEADF) lav = ev + lsum;
-            lav = (lav > MB_DEADF) ? lav : MB_NEG;
-            la = lav;
-            R = (Rn != MB_DEADM) ? Rn : R;
-            float *lp = (lead && j1 >= 1) ? p.log_alpha + ro + (j1 - 1) : reinterpret_cast<float *>(trash);
-            *lp = (lav > MB_DEADF) ? lav * MB_LN2 : -__builtin_huge_valf();
-        }
-    };
-#pragma unroll 1
-    for (int i = i0; i <= i1; i += 2) {
-        do_row(i, e_n1, L_n1);
-        if (i + 1 > i1) break;
-        do_row(i + 1, e_n2, L_n2);
-    }
-    if (i1 + 1 < I) {
-        const int i = i1 + 1;
-        if (publishes) {
-            const float Lr = p.Lw[ubase + (size_t)i * p.Ty + kl];
-            const float L = (j1 < J) ? Lr : MB_NEG;
-            const float u = (L > MB_DEADF && la > MB_DEADF) ? la - L : MB_NEG;
-            int M;
-            float sm;
-            mb_encode(u, M, sm);
-            unsigned *r = ring_out + (size_t)i * 3 * D + (j1 - (bnd - D));
-            mb_ring_store(r, __builtin_bit_cast(unsigned, (float)M));
-            mb_ring_store(r + D, __builtin_bit_cast(unsigned, sm));
-        }
-        if (lead && j1 >= 1) p.log_alpha[ubase + (size_t)i * p.Ty + (j1 - 1)] = -__builtin_huge_valf();
-        dead_rows(i1 + 2, I);
-    }
+    mb_split_chain<VT, H, true, false, true, false>(p);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1742,6 +1377,39 @@ static int mobo_bwd_plan(int B, int Tx, int Ty, int max_duration, MoboBwdPlan &p
     return ALIGNER_OK;
 }
 
+// what the search and its gradient check alike before they plan; vt: the energies' type as the kernels' VT
+static int mobo_check(int energy_dtype, int max_duration, int B, int Tx, int Ty, int &vt) {
+    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (max_duration < 1) return fail(ALIGNER_EINVAL, "max_duration %d < 1", max_duration);
+    vt = energy_dtype == ALIGNER_DT_F32 ? 0 : energy_dtype == ALIGNER_DT_BF16 ? 1 : energy_dtype == ALIGNER_DT_F16 ? 2 : -1;
+    if (vt < 0) return fail(ALIGNER_EINVAL, "energy dtype %d not supported (F32, BF16, F16)", energy_dtype);
+    return ALIGNER_OK;
+}
+static int mobo_check_grid(int max_duration, int B, int Tx, int Ty) {
+    if (B > 65535 || Tx > 65535) return fail(ALIGNER_EDOM, "grid too large");
+    if ((max_duration > Ty ? Ty : max_duration) > 65535) return fail(ALIGNER_EDOM, "max_duration %d too large", max_duration);
+    return ALIGNER_OK;
+}
+
+// LDS of the kernels that stage MB_NCH + D entries of a row (the normalisers, the gradient's last pass)
+static int mobo_row_lds(int D, size_t &nlds) {
+    nlds = (size_t)(MB_NCH + D + 4) * 12;
+    if (nlds > (size_t)device_lds_limit()) return fail(ALIGNER_EDOM, "max_duration %d needs %zu bytes of LDS", D, nlds);
+    return ALIGNER_OK;
+}
+
+// the normalisers (the kernel also refills the ring and clears the give-up words)
+static int mobo_launch_norm(const MoboParams &p, int vt, size_t nlds, size_t ring_words, hipStream_t s) {
+    const dim3 grid((p.Ty + MB_NCH - 1) / MB_NCH, p.Tx, p.B);
+    auto launch = [&](auto kern) -> int {
+        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), nlds));
+        hipLaunchKernelGGL(kern, grid, dim3(256), nlds, s, p, (unsigned long long)ring_words);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+        return ALIGNER_OK;
+    };
+    return vt == 0 ? launch(mobo_norm_kernel<0>) : vt == 1 ? launch(mobo_norm_kernel<1>) : launch(mobo_norm_kernel<2>);
+}
+
 }  // namespace aligner
 
 using namespace aligner;
@@ -1761,13 +1429,10 @@ int aligner_boundary_search_backward(const void *energies, int energy_dtype, con
                                      size_t workspace_bytes, int B, int Tx, int Ty, void *stream) {
     if (!energies || !t_xs || !t_ys || !log_alpha || !grad_energies_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
     if (!grad_log_alpha && !grad_gamma) return fail(ALIGNER_EINVAL, "no cotangent: grad_log_alpha and grad_gamma are both null");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
-    if (max_duration < 1) return fail(ALIGNER_EINVAL, "max_duration %d < 1", max_duration);
-    const int vt = energy_dtype == ALIGNER_DT_F32 ? 0 : energy_dtype == ALIGNER_DT_BF16 ? 1 : energy_dtype == ALIGNER_DT_F16 ? 2 : -1;
-    if (vt < 0) return fail(ALIGNER_EINVAL, "energy dtype %d not supported (F32, BF16, F16)", energy_dtype);
+    int vt;
+    if (const int rc = mobo_check(energy_dtype, max_duration, B, Tx, Ty, vt)) return rc;
     if (B == 0) return ALIGNER_OK;
-    if (B > 65535 || Tx > 65535) return fail(ALIGNER_EDOM, "grid too large");
-    if ((max_duration > Ty ? Ty : max_duration) > 65535) return fail(ALIGNER_EDOM, "max_duration %d too large", max_duration);
+    if (const int rc = mobo_check_grid(max_duration, B, Tx, Ty)) return rc;
     MoboBwdPlan pl;
     const int prc = mobo_bwd_plan(B, Tx, Ty, max_duration, pl, false);
     if (prc) return prc;
@@ -1776,9 +1441,9 @@ int aligner_boundary_search_backward(const void *energies, int energy_dtype, con
     if (workspace_bytes < pl.total) return fail(ALIGNER_ENOSPC, "workspace %zu < %zu bytes", workspace_bytes, pl.total);
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t nlds = (size_t)(MB_NCH + f.D + 4) * 12;
-    if (nlds > (size_t)device_lds_limit()) return fail(ALIGNER_EDOM, "max_duration %d needs %zu bytes of LDS", f.D, nlds);
-    {   // 1. normalisers (the search's kernel; it also refills the ring and clears the give-up words)
+    size_t nlds;
+    if (const int rc = mobo_row_lds(f.D, nlds)) return rc;
+    {   // 1. normalisers (the search's kernel)
         MoboParams p{};
         p.e = energies;  p.t_xs = t_xs;  p.t_ys = t_ys;
         p.Lw = reinterpret_cast<float *>(ws + pl.L_off);
@@ -1786,15 +1451,7 @@ int aligner_boundary_search_backward(const void *energies, int energy_dtype, con
         p.failw = reinterpret_cast<int *>(ws + pl.fail_off);
         p.status = reinterpret_cast<int *>(ws + pl.status_off);
         p.B = B;  p.Tx = Tx;  p.Ty = Ty;  p.D = f.D;  p.S = f.S;  p.nmax = f.nmax;
-        const dim3 grid((Ty + MB_NCH - 1) / MB_NCH, Tx, B);
-        auto launch = [&](auto kern) -> int {
-            ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), nlds));
-            hipLaunchKernelGGL(kern, grid, dim3(256), nlds, s, p, (unsigned long long)pl.ring_words);
-            ALIGNER_HIP_CHECK(hipGetLastError());
-            return ALIGNER_OK;
-        };
-        const int rc = vt == 0 ? launch(mobo_norm_kernel<0>) : vt == 1 ? launch(mobo_norm_kernel<1>) : launch(mobo_norm_kernel<2>);
-        if (rc) return rc;
+        if (const int rc = mobo_launch_norm(p, vt, nlds, pl.ring_words, s)) return rc;
     }
     float *Gw = reinterpret_cast<float *>(ws + pl.G_off);
     MoboBwdParams q{energies, t_xs, t_ys, log_alpha, grad_log_alpha, grad_gamma, grad_energies_out,
@@ -1865,14 +1522,11 @@ int aligner_boundary_search(const void *energies, int energy_dtype, const int32_
     if (!boundaries_out && !log_alpha_out) return fail(ALIGNER_EINVAL, "nothing asked for: boundaries_out and log_alpha_out are both null");
     if (!boundaries_out && (durations_out || map_score_out))
         return fail(ALIGNER_EINVAL, "durations / map_score need boundaries_out (the MAP sequence is searched or it is not)");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
-    if (max_duration < 1) return fail(ALIGNER_EINVAL, "max_duration %d < 1", max_duration);
-    const int vt = energy_dtype == ALIGNER_DT_F32 ? 0 : energy_dtype == ALIGNER_DT_BF16 ? 1 : energy_dtype == ALIGNER_DT_F16 ? 2 : -1;
-    if (vt < 0) return fail(ALIGNER_EINVAL, "energy dtype %d not supported (F32, BF16, F16)", energy_dtype);
+    int vt;
+    if (const int rc = mobo_check(energy_dtype, max_duration, B, Tx, Ty, vt)) return rc;
     if (gamma_out && !log_alpha_out) return fail(ALIGNER_EINVAL, "gamma needs the log_alpha buffer as well");
     if (B == 0) return ALIGNER_OK;
-    if (B > 65535 || Tx > 65535) return fail(ALIGNER_EDOM, "grid too large");
-    if ((max_duration > Ty ? Ty : max_duration) > 65535) return fail(ALIGNER_EDOM, "max_duration %d too large", max_duration);
+    if (const int rc = mobo_check_grid(max_duration, B, Tx, Ty)) return rc;
     MoboPlan pl;
     const int prc = mobo_plan(B, Tx, Ty, max_duration, pl, false);
     if (prc) return prc;
@@ -1887,17 +1541,9 @@ int aligner_boundary_search(const void *energies, int energy_dtype, const int32_
                  reinterpret_cast<int *>(ws + pl.status_off), B, Tx, Ty, pl.D, pl.S, pl.nmax, pl.bstride, g_opt_mobo_start_lag, g_debug_stamps,
                  g_opt_mobo_drop_segment, g_opt_mobo_drop_segment >= 0 ? 2048 : MB_SPIN_LIMIT};
     {   // 1. normalisers (+ ring refill)
-        const size_t nlds = (size_t)(MB_NCH + pl.D + 4) * 12;
-        if (nlds > (size_t)device_lds_limit()) return fail(ALIGNER_EDOM, "max_duration %d needs %zu bytes of LDS", pl.D, nlds);
-        const dim3 grid((Ty + MB_NCH - 1) / MB_NCH, Tx, B);
-        auto launch = [&](auto kern) -> int {
-            ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), nlds));
-            hipLaunchKernelGGL(kern, grid, dim3(256), nlds, s, p, (unsigned long long)pl.ring_words);
-            ALIGNER_HIP_CHECK(hipGetLastError());
-            return ALIGNER_OK;
-        };
-        const int rc = vt == 0 ? launch(mobo_norm_kernel<0>) : vt == 1 ? launch(mobo_norm_kernel<1>) : launch(mobo_norm_kernel<2>);
-        if (rc) return rc;
+        size_t nlds;
+        if (const int rc = mobo_row_lds(pl.D, nlds)) return rc;
+        if (const int rc = mobo_launch_norm(p, vt, nlds, pl.ring_words, s)) return rc;
     }
     {   // 2. the chain
         auto launch = [&](auto kern) -> int {
@@ -1908,7 +1554,7 @@ int aligner_boundary_search(const void *energies, int energy_dtype, const int32_
         };
         int rc;
 #define MB_LAUNCH_NP(VT_)                                                                               \
-    (pl.NP != 1 ? launch(mobo_chain_kernel<VT_, true>)                                                  \
+    (pl.NP != 1 ? launch(mobo_chain_kernel<VT_>)                                                \
      : (!boundaries_out && !g_opt_mobo_full_chain && !g_debug_stamps) ? MB_LAUNCH_SUM(VT_)              \
      : log_alpha_out ? MB_LAUNCH_H(VT_, true)                                                           \
      : (g_opt_mobo_full_chain || g_debug_stamps) ? MB_LAUNCH_H(VT_, false) : MB_LAUNCH_MAP(VT_))

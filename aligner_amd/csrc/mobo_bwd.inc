@@ -116,18 +116,13 @@ struct MbBwdSeg {                       // a block's segment of its utterance (t
 };
 __device__ __forceinline__ MbBwdSeg mb_bwd_segment(const MoboBwdParams &p, int b, int sr) {
     MbBwdSeg g;
-    g.I = p.t_xs[b];
-    g.J = p.t_ys[b];
-    g.I = g.I > p.Tx ? p.Tx : g.I;
-    g.J = g.J > p.Ty ? p.Ty : g.J;
-    g.valid = g.I >= 1 && g.J >= g.I && (long long)g.J <= (long long)g.I * p.D;
+    g.valid = mb_lengths(p.t_xs, p.t_ys, p.Tx, p.Ty, p.D, b, g.I, g.J);
     g.a = g.bnd = g.nloc = g.sg = g.Sne = 0;
     g.has_src = g.has_dst = false;
     if (!g.valid) return g;
     const int P = g.J + 1;
-    int Sb = P / p.D;
-    Sb = Sb < 1 ? 1 : (Sb > p.S ? p.S : Sb);
-    const int n = (P + Sb - 1) / Sb;
+    int Sb, n;
+    mb_cut(g.J, p.D, p.S, Sb, n);
     g.Sne = (P + n - 1) / n;                       // segments that hold a position
     if (sr >= g.Sne) {
         g.valid = false;

@@ -113,10 +113,23 @@ def test_boundary_search_matches_oracle(dev, B, Tx, Ty, D):
     _check_against_oracle(dev, e, tx, ty, D)
 
 
+# The three split-form chain kernels are one body, and the two tests below are what shows that its instantiations agree, so
+# their shapes reach every (lanes per position H, helper wave) pair of the launch plan (mobo_plan; P = Ty + 1 positions,
+# S = min(CUs / B, P / D, ceil(P / 64)) segments, nmax = max(ceil(P / S), min(2 D, P)) positions in the largest; H = 4 up
+# to nmax = 64, 2 up to 128, else 1; a helper wave when S > 1; figures for 256 CUs).  The other shapes give H = 4 with
+# (e.g. (3, 40, 300, 16): S = 5, nmax = 61) and without a helper ((4, 12, 40, 8): S = 1, nmax = 41) and H = 2 with one
+# ((2, 30, 1100, 64): S = 17, nmax = 128); these add the rest.  The coverage holds on a device of 256 CUs with the
+# `mobo_lanes` debug option unset, and nothing here asserts where a shape landed: on another device the tests still
+# compare the kernels that the plan picks there, but may miss a pair.
+SPLIT_FORM_SHAPES = [(1, 12, 600, 100),    # P = 601, S = min(256, 6, 10) = 6, nmax = max(101, 200) = 200: H = 1, helper
+                     (1, 4, 300, 200),     # P = 301, S = 1, nmax = 301: H = 1, no helper
+                     (1, 4, 100, 60)]      # P = 101, S = 1, nmax = 101: H = 2, no helper
+
+
 @gpu
 @pytest.mark.parametrize("B,Tx,Ty,D", [(3, 1, 1, 1), (2, 5, 9, 3), (4, 12, 40, 8), (3, 40, 300, 16), (2, 64, 257, 32),
                                        (2, 30, 1100, 64), (1, 100, 600, 7), (1, 120, 1000, 16), (5, 33, 700, 40),
-                                       (2, 8, 1500, 800), (8, 500, 4000, 32), (300, 4, 20, 6)])
+                                       (2, 8, 1500, 800), (8, 500, 4000, 32), (300, 4, 20, 6)] + SPLIT_FORM_SHAPES)
 def test_map_only_chain_equals_the_full_chain(dev, B, Tx, Ty, D):
     """Without log_alpha the search runs the max-product chain alone (mobo_chain_map_kernel); the same arithmetic as the
     max-product half of the full kernel, so boundaries, durations and the score are bit for bit the full kernel's
@@ -153,7 +166,7 @@ def test_map_only_chain_equals_the_full_chain(dev, B, Tx, Ty, D):
 @gpu
 @pytest.mark.parametrize("B,Tx,Ty,D", [(3, 1, 1, 1), (2, 5, 9, 3), (4, 12, 40, 8), (3, 40, 300, 16), (2, 64, 257, 32),
                                        (2, 30, 1100, 64), (1, 100, 600, 7), (1, 120, 1000, 16), (5, 33, 700, 40),
-                                       (2, 8, 1500, 800), (1, 6, 2600, 1300), (300, 4, 20, 6)])
+                                       (2, 8, 1500, 800), (1, 6, 2600, 1300), (300, 4, 20, 6)] + SPLIT_FORM_SHAPES)
 @pytest.mark.parametrize("scale", [2.0, 30.0])
 def test_sum_only_chain_equals_the_full_chain(dev, B, Tx, Ty, D, scale):
     """want_map=False runs the sum-product chain alone (mobo_chain_sum_kernel): log_alpha and gamma bit for bit the full

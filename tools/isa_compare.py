@@ -5,7 +5,10 @@ identical or different -- for a different one the count of changed lines (also w
 leaves the changes that are not a renaming) and its row of the build's resource report
 (aligner_amd/lib/obj/*.resources.txt: both trees must have been built) before and after.
 
-    python tools/isa_compare.py /path/to/parent/checkout [/path/to/this/tree] > profiles/NAME_isa.txt
+    python tools/isa_compare.py [--rename=REGEX=REPL] /path/to/parent/checkout [/path/to/this/tree] > profiles/NAME_isa.txt
+
+A kernel that lost or gained a template parameter has another mangled name: `--rename` rewrites the parent's names
+(`re.sub` on its assembly and its resource rows) so that it is compared with its successor.
 
 The one line a compiler changes for any edit of a file or of a header it includes, the hash in the `__hip_cuid_` symbol,
 is masked."""
@@ -46,11 +49,13 @@ def assembly(tree, out):
     return srcs
 
 
-def functions(path):
+def functions(path, renames=()):
     """{name: lines} of every function of an assembly file, and the lines outside them."""
     funcs, rest, name, declared = {}, [], None, set()
     for line in open(path):
         line = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", line)
+        for old, new in renames:
+            line = re.sub(old, new, line)
         m = re.match(r"\s*\.type\s+(\w+),@function", line)
         if m:
             declared.add(m.group(1))
@@ -95,19 +100,25 @@ def row(res, name, path):
 
 
 def main():
-    parent = os.path.abspath(sys.argv[1])
-    this = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    renames = [a[len("--rename="):].split("=", 1) for a in sys.argv[1:] if a.startswith("--rename=")]
+    paths = [a for a in sys.argv[1:] if not a.startswith("--rename=")]
+    if any(len(r) != 2 for r in renames) or not paths:
+        raise SystemExit("usage: isa_compare.py [--rename=REGEX=REPL ...] PARENT_TREE [THIS_TREE]")
+    parent = os.path.abspath(paths[0])
+    this = os.path.abspath(paths[1]) if len(paths) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with tempfile.TemporaryDirectory() as a, tempfile.TemporaryDirectory() as b:
         srcs = assembly(parent, a)
         assert srcs == assembly(this, b), "the two trees have different kernel files"
         same = diff = 0
         for src in srcs:
-            (fa, ra), (fb, rb) = functions(os.path.join(a, src + ".s")), functions(os.path.join(b, src + ".s"))
-            assert list(fa) == list(fb), src + ": the two builds have different functions"
+            (fa, ra), (fb, rb) = functions(os.path.join(a, src + ".s"), renames), functions(os.path.join(b, src + ".s"))
+            assert sorted(fa) == sorted(fb), src + ": the two builds have different functions"
             # (outside the functions: the kernel descriptors and the metadata, which repeat a different function's sizes)
             lone = ra != rb and fa == fb
             print("%s: %d functions%s" % (src, len(fa), "; DIFFERENT outside the functions only" if lone else ""))
             res_a, res_b = resources(parent, src), resources(this, src)
+            for old, new in renames:
+                res_a = {re.sub(old, new, k): v for k, v in res_a.items()}
             for name in fa:
                 rows = row(res_a, name, os.path.join(a, src + ".s")), row(res_b, name, os.path.join(b, src + ".s"))
                 if fa[name] == fb[name] and rows[0] == rows[1]:
