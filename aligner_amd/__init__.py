@@ -22,6 +22,7 @@ from .pausepath import PauseAlignment, align_with_pauses  # noqa: F401
 from .gausslogp import gaussian_align, gaussian_forward_sum_loss, gaussian_logp, gaussian_logp_backward  # noqa: F401
 from .gaussnll import gaussian_nll, gaussian_nll_loss  # noqa: F401
 from .gaussup import gaussian_upsample, gaussian_upsample_at  # noqa: F401
+from .softdtw import soft_dtw, soft_dtw_loss  # noqa: F401
 
 __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status",
            "soft_attention", "soft_attention_backward", "conv1d", "conv1d_backward", "alignment_encoder", "AlignmentEncoderParams",
@@ -29,7 +30,7 @@ __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status"
            "boundary_search", "boundary_search_backward", "soft_boundaries", "BoundarySearch",
            "align_with_pauses", "PauseAlignment", "gaussian_logp", "gaussian_logp_backward", "gaussian_forward_sum_loss",
            "gaussian_align", "gaussian_nll", "gaussian_nll_loss",
-           "gaussian_upsample", "gaussian_upsample_at",
+           "gaussian_upsample", "gaussian_upsample_at", "soft_dtw", "soft_dtw_loss",
            "install_dropin"]
 
 

@@ -115,6 +115,8 @@ SIGNATURES = {
     "aligner_gauss_upsample_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "aligner_gauss_upsample_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                                  _i, _i, _i, _i, _vp]),
+    "aligner_soft_dtw_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aligner_soft_dtw_f32": (_i, [_vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 

@@ -1,0 +1,337 @@
+// Soft-DTW (Cuturi & Blondel 2017) between two frame sequences of different lengths, and its expected alignment
+// matrix E = d value / d cost (Mensch & Blondel 2018); DESIGN.md 5.7.  Build-defined: include/aligner_amd.h has the
+// definition (band |i - j| <= w, warp penalty on the two stalling moves, +inf costs as forbidden cells).
+//
+//     R[i,j] = D[i,j] + softmin_gamma(R[i-1,j-1], R[i-1,j] + p, R[i,j-1] + p)        value = R[n-1,m-1]
+//
+// One workgroup per utterance, one lane per row, a wave per 64 rows, and nothing shared between workgroups.  The
+// lanes are skewed: at its local step s wave w's lane l sits on column s - l of row 64 w + l, so R[i-1,j] is what the
+// lane below computed in the step before (one wave_shr per step), R[i-1,j-1] what it handed over the step before
+// that, and R[i,j-1] the lane's own register.  A wave's last row reaches the next wave through a ring in LDS; the
+// waves run SD_LAG tiles of SD_TW steps apart (the skew makes a wave's last row 63 steps late) with one barrier per
+// tile.  Costs come through LDS in the skewed order -- position c of row r of tile t is column t SD_TW + c - r, a
+// 64-byte segment of the row in memory -- at a pitch of SD_TW + 1 floats, so the 64 lanes of a step read 64 banks;
+// R (for the gradient) leaves through the same tile.
+//
+// Arithmetic: base-2 logs with log2(e) / gamma folded into the costs on their way in, "+inf" the finite SD_BIG
+// (it absorbs every addend, nothing computes inf - inf), every cell's result clamped to [-SD_BIG, SD_BIG].
+//
+// Backward never reads the costs.  It sweeps the same skew in reverse with E[n-1,m-1] = 1: cell (i,j) takes the three
+// stored predecessor values, forms the softmin's own weights 2^(mn - pred) / sum (mn their minimum) and pushes
+// E[i,j] times each to that predecessor.  Two of the three go to the lane below, added up and moved by one wave_shl a
+// step.  Only differences of neighbouring R values enter, so the flow is conserved (E[0,0] = 1 up to rounding) where
+// the textbook recursion exp((R[succ] - R[i,j] - D[succ]) / gamma) loses it to cancellation.  R[i,j] is dead once
+// (i,j) and its three successors are done: E overwrites R in place in the gradient buffer.
+#include "common.h"
+#include "device.h"
+
+namespace aligner {
+
+constexpr int   SD_TW = 16;                               // steps (and staged floats per row) per tile
+constexpr int   SD_PITCH = SD_TW + 1;                     // odd: a step's 64 lanes read 64 banks
+constexpr int   SD_LAG = (63 + SD_TW - 1) / SD_TW + 1;    // tiles between neighbouring waves
+constexpr int   SD_RS = 64 / SD_TW;                       // rows a wave moves per pass of a tile
+constexpr int   SD_RING = 64;                             // hand-off ring of a wave, entries (a column each)
+constexpr int   SD_MAX_N = 1024;
+constexpr float SD_BIG = 1e30f;                           // "+inf" in scaled units
+constexpr int   SD_NO_BAND = 1 << 30;
+
+struct SoftDtwParams {
+    const float *cost;      // [B,N,M]
+    const int   *ns, *ms;   // [B] or null
+    float scale;            // log2(e) / gamma
+    float pen;              // warp penalty, scaled
+    float unscale;          // gamma ln 2
+    int   band;             // SD_NO_BAND: none
+    float *value;           // [B]
+    float *grad;            // [B,N,M]: R (scaled) after forward, E after backward; null: value only
+    float *fin;             // workspace [B]: R[n-1,m-1] scaled, SD_BIG without an alignment
+    int B, N, M;
+};
+
+// lane i <- src[lane i-1], lane 0 gets `edge` (wave_shr:1); lane i <- src[lane i+1], lane 63 gets `edge` (wave_shl:1)
+__device__ __forceinline__ float sd_from_below(float edge, float src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge),
+                                                                 __builtin_bit_cast(int, src), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float sd_from_above(float edge, float src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge),
+                                                                 __builtin_bit_cast(int, src), 0x130, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float sd_lane(float v, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+// a wave's own LDS traffic in program order, for the compiler as well (lanes read what other lanes of the wave wrote)
+__device__ __forceinline__ void sd_wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// utterance b's lengths within the block; false: no alignment (a length below 1, or the corner outside the band)
+__device__ __forceinline__ bool sd_lengths(const SoftDtwParams &p, int b, int &n, int &m) {
+    n = p.ns ? p.ns[b] : p.N;
+    m = p.ms ? p.ms[b] : p.M;
+    n = n < p.N ? n : p.N;
+    m = m < p.M ? m : p.M;
+    if (n < 1 || m < 1) return false;
+    const int d = n > m ? n - m : m - n;
+    return d <= p.band;
+}
+
+// the columns of row i that exist: [jlo, jhi], empty for a row past the utterance
+__device__ __forceinline__ void sd_row_span(int i, int n, int m, int band, int &jlo, int &jhi) {
+    jlo = i - band > 0 ? i - band : 0;
+    jhi = i + band < m - 1 ? i + band : m - 1;
+    if (i >= n) { jlo = 1; jhi = 0; }
+}
+
+// the three softmin weights 2^(mn - x), mn the smallest operand (so one of them is 1 and the sum is in [1, 3])
+__device__ __forceinline__ float sd_weights(float a, float b, float c, float &wa, float &wb, float &wc) {
+    const float mn = fminf(fminf(a, b), c);
+    wa = __builtin_amdgcn_exp2f(mn - a);
+    wb = __builtin_amdgcn_exp2f(mn - b);
+    wc = __builtin_amdgcn_exp2f(mn - c);
+    return mn;
+}
+
+__global__ __launch_bounds__(SD_MAX_N) void softdtw_forward_kernel(SoftDtwParams p) {
+    extern __shared__ __attribute__((aligned(16))) float sd_smem[];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), NW = blockDim.x >> 6;
+    int n, m;
+    if (!sd_lengths(p, b, n, m)) {
+        if (tid == 0) { p.value[b] = __builtin_huge_valf(); p.fin[b] = SD_BIG; }
+        return;
+    }
+    const int nw = (n + 63) >> 6;                             // waves that own rows of this utterance
+    const bool active = w < nw;
+    float *tile = sd_smem + w * 64 * SD_PITCH;                // [64][SD_PITCH] this wave's costs, then its R
+    float *ring = sd_smem + NW * 64 * SD_PITCH;               // [NW][SD_RING] each wave's last row, by column
+    const int ntl = (m + 64 + SD_TW - 1) / SD_TW;             // steps 0 .. m + 62 reach every cell of 64 skewed rows
+    const int nph = ntl + SD_LAG * (nw - 1) + 1;
+    const size_t ubase = (size_t)b * p.N * p.M;
+    const float *cost = p.cost + ubase;
+    float *R = p.grad ? p.grad + ubase : nullptr;
+    const int i = 64 * w + lane;
+    int jlo, jhi;
+    sd_row_span(i, n, m, p.band, jlo, jhi);
+    // the movers' element k of a tile: row r0 + SD_RS k of the wave at position c0, SD_RS rows a pass (a 64-byte segment
+    // of a row per 16 lanes); its column at tile t is t SD_TW + col0 - SD_RS k and its place in memory moves by kstride
+    const int r0 = lane / SD_TW, c0 = lane % SD_TW, row0 = 64 * w + r0, col0 = c0 - r0;
+    const int off0 = row0 * p.M + col0, kstride = SD_RS * (p.M - 1), lds0 = r0 * SD_PITCH + c0;
+    float prev = SD_BIG;                                      // R[i,j-1]
+    float upprev = i == 0 ? 0.f : SD_BIG;                     // R[i-1,j-1]; R[-1,-1] = 0
+    float fin = SD_BIG;
+    for (int ph = 0; ph < nph; ++ph) {
+        const int t = ph - SD_LAG * w - 1;                    // (the phase before a wave's first tile stages that tile)
+        const bool ldnext = active && t + 1 >= 0 && t + 1 < ntl;
+        float v[SD_TW];
+        if (ldnext) {
+#pragma unroll
+            for (int k = 0; k < SD_TW; ++k) {
+                const int row = row0 + SD_RS * k, col = (t + 1) * SD_TW + col0 - SD_RS * k;
+                float d = SD_BIG;
+                if (row < n && col >= 0 && col < m) d = cost[off0 + (t + 1) * SD_TW + k * kstride];
+                v[k] = fminf(fmaxf(d * p.scale, -SD_BIG), SD_BIG);
+            }
+        }
+        if (active && t >= 0 && t < ntl) {
+            float bv = SD_BIG;                                // the row above this wave's first, columns of this tile
+            if (w > 0 && lane < SD_TW) {
+                const int col = t * SD_TW + lane;
+                if (col < m) bv = ring[(w - 1) * SD_RING + (col & (SD_RING - 1))];
+            }
+            float dv[SD_TW];                                  // (read up front: behind the stores of R below, the compiler
+#pragma unroll                                                //  keeps each read in its own step and waits for it there)
+            for (int c = 0; c < SD_TW; ++c) dv[c] = tile[lane * SD_PITCH + c];
+#pragma unroll
+            for (int c = 0; c < SD_TW; ++c) {
+                const int j = t * SD_TW + c - lane;
+                const float d = dv[c];
+                const float up = sd_from_below(sd_lane(bv, c), prev);
+                float wa, wb, wc;
+                const float mn = sd_weights(upprev, up + p.pen, prev + p.pen, wa, wb, wc);
+                float cur = d + (mn - __builtin_amdgcn_logf((wa + wb) + wc));
+                cur = __builtin_amdgcn_fmed3f(cur, -SD_BIG, SD_BIG);
+                const bool valid = j >= jlo && j <= jhi;
+                cur = valid ? cur : SD_BIG;
+                if (R) tile[lane * SD_PITCH + c] = cur;
+                // (columns below 0 land on entries nobody reads yet: the next wave starts SD_LAG tiles later and masks them)
+                if (lane == 63) ring[w * SD_RING + (j & (SD_RING - 1))] = cur;
+                if (valid && j == m - 1 && i == n - 1) fin = cur;
+                upprev = up;
+                prev = cur;
+            }
+            if (R) {
+                sd_wave_lds_sync();
+#pragma unroll
+                for (int k = 0; k < SD_TW; ++k) {
+                    const int row = row0 + SD_RS * k, col = t * SD_TW + col0 - SD_RS * k;
+                    if (row < n && col >= 0 && col < m) R[off0 + t * SD_TW + k * kstride] = tile[lds0 + k * SD_RS * SD_PITCH];
+                }
+            }
+        }
+        if (ldnext) {
+#pragma unroll
+            for (int k = 0; k < SD_TW; ++k) tile[lds0 + k * SD_RS * SD_PITCH] = v[k];
+        }
+        lds_barrier();
+    }
+    if (i == n - 1) {
+        p.fin[b] = fin;
+        p.value[b] = fin < 0.5f * SD_BIG ? fin * p.unscale : __builtin_huge_valf();
+    }
+}
+
+__global__ __launch_bounds__(SD_MAX_N) void softdtw_backward_kernel(SoftDtwParams p) {
+    extern __shared__ __attribute__((aligned(16))) float sd_smem[];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), NW = blockDim.x >> 6;
+    int n, m;
+    const bool some = sd_lengths(p, b, n, m) && p.fin[b] < 0.5f * SD_BIG;
+    const size_t ubase = (size_t)b * p.N * p.M;
+    float *E = p.grad + ubase;
+    // exact zeros outside the utterance (the sweep below writes every cell inside it), everywhere without an alignment
+    for (int r = w; r < p.N; r += NW)
+        for (int c = ((some && r < n) ? m : 0) + lane; c < p.M; c += 64) E[r * p.M + c] = 0.f;
+    if (!some) return;
+    const int nw = (n + 63) >> 6;
+    const bool active = w < nw;
+    float *tile = sd_smem + w * 65 * SD_PITCH;                // [65][SD_PITCH]: row 0 is the row above the wave's first
+    float *ring = sd_smem + NW * 65 * SD_PITCH;               // [NW][SD_RING] what a wave's first row sends up, by column
+    const int ntl = (m + 64 + SD_TW - 1) / SD_TW;             // one step beyond the forward sweep's: the look-ahead below
+    const int nph = ntl + SD_LAG * (nw - 1) + 1;
+    const int i = 64 * w + lane;
+    int jlo, jhi;
+    sd_row_span(i, n, m, p.band, jlo, jhi);
+    const int r0 = lane / SD_TW, c0 = lane % SD_TW, row0 = 64 * w + r0, col0 = c0 - r0;         // (as in the forward kernel)
+    const int off0 = row0 * p.M + col0, kstride = SD_RS * (p.M - 1), lds0 = r0 * SD_PITCH + c0;
+    float rm1 = SD_BIG, xprev = SD_BIG;                       // R[i,j-1], R[i-1,j]
+    float cl = 0.f, cdprev = 0.f, send = 0.f;                 // flow to (i,j-1); to (i-1,j-1) from the step before; to the lane below
+    for (int ph = 0; ph < nph; ++ph) {
+        const int t = ntl - 1 - (ph - SD_LAG * (nw - 1 - w) - 1);      // tiles from the last to the first
+        const bool ldnext = active && t - 1 >= 0 && t - 1 < ntl;
+        float v[SD_TW + 1];
+        if (ldnext) {
+            // position c of row r (-1 .. 63) of tile t-1 is R[64 w + r, (t-1) SD_TW + c - 2 - r]: two columns ahead of
+            // the cell the lane is on, since a cell's weights need R[i,j-1] and the lane above R[i,j-2]
+#pragma unroll
+            for (int k = 0; k < SD_TW + 1; ++k) {
+                const int row = row0 - 1 + SD_RS * k, col = (t - 1) * SD_TW - 1 + col0 - SD_RS * k;
+                float x = SD_BIG;
+                if (k < SD_TW || lane < SD_TW) {
+                    if (row < 0) x = col == -1 ? 0.f : SD_BIG;                        // R[-1,-1] = 0
+                    else if (row < n && col >= 0 && col < m) x = E[off0 - p.M - 1 + (t - 1) * SD_TW + k * kstride];
+                }
+                v[k] = x;
+            }
+        }
+        if (active && t >= 0 && t < ntl) {
+            float rv = 0.f;                                   // what the wave below sends to this wave's last row
+            if (w + 1 < nw && lane < SD_TW) {
+                const int col = t * SD_TW + lane - 63;
+                if (col >= 0 && col < m) rv = ring[(w + 1) * SD_RING + (col & (SD_RING - 1))];
+            }
+            // Four steps at a time (unrolled whole, the kernel spills), their operands read up front: behind the stores
+            // of E below, each read would wait in its own step.  The row above the wave's first: one entry per lane.
+            const float above = tile[lane & (SD_TW - 1)];
+#pragma unroll 1
+            for (int c4 = SD_TW - 4; c4 >= 0; c4 -= 4) {
+                float r2v[4];
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) r2v[cc] = tile[(lane + 1) * SD_PITCH + c4 + cc];
+#pragma unroll
+                for (int cc = 3; cc >= 0; --cc) {
+                    const int c = c4 + cc;
+                    const int j = t * SD_TW + c - lane;
+                    const float r2 = r2v[cc];                                             // R[i,j-2]
+                    const float x = sd_from_below(sd_lane(above, c), r2);                 // R[i-1,j-1]
+                    float wa, wb, wc;
+                    sd_weights(x, xprev + p.pen, rm1 + p.pen, wa, wb, wc);
+                    const float inv = __builtin_amdgcn_rcpf((wa + wb) + wc);
+                    float e = cl + sd_from_above(sd_lane(rv, c), send);
+                    if (j == m - 1 && i == n - 1) e = 1.f;
+                    e = (j >= jlo && j <= jhi) ? e : 0.f;
+                    const float q = e * inv;
+                    const float cd = q * wa, cu = q * wb;
+                    cl = q * wc;
+                    send = cu + cdprev;                                                   // both land on (i-1,j)
+                    cdprev = cd;
+                    tile[(lane + 1) * SD_PITCH + c] = e;
+                    if (lane == 0) ring[w * SD_RING + (j & (SD_RING - 1))] = send;
+                    xprev = x;
+                    rm1 = r2;
+                }
+            }
+            sd_wave_lds_sync();
+#pragma unroll
+            for (int k = 0; k < SD_TW; ++k) {
+                const int row = row0 + SD_RS * k, col = t * SD_TW + col0 - SD_RS * k;
+                if (row < n && col >= 0 && col < m) E[off0 + t * SD_TW + k * kstride] = tile[lds0 + (k * SD_RS + 1) * SD_PITCH];
+            }
+            sd_wave_lds_sync();
+        }
+        if (ldnext) {
+#pragma unroll
+            for (int k = 0; k < SD_TW + 1; ++k)
+                if (k < SD_TW || lane < SD_TW) tile[lds0 + k * SD_RS * SD_PITCH] = v[k];
+        }
+        lds_barrier();
+    }
+}
+
+static bool sd_shape_ok(int B, int N, int M) {
+    return B >= 1 && N >= 1 && M >= 1 && B <= 65535 && N <= SD_MAX_N && (long long)N * M < (1ll << 29);
+}
+static size_t sd_lds_bytes(int NW, bool backward) {
+    return (size_t)NW * ((backward ? 65 : 64) * SD_PITCH + SD_RING) * sizeof(float);
+}
+
+}  // namespace aligner
+
+using namespace aligner;
+
+extern "C" {
+
+size_t aligner_soft_dtw_workspace_bytes(int B, int N, int M, int want_grad) {
+    (void)want_grad;                                          // R lives in the gradient buffer: one float per utterance either way
+    if (!sd_shape_ok(B, N, M)) return 0;
+    return align_up((size_t)B * sizeof(float), 256);
+}
+
+int aligner_soft_dtw_f32(const float *cost, const int32_t *n_dev, const int32_t *m_dev, float gamma, float warp_penalty,
+                         int bandwidth, float *value_out, float *grad_out, void *workspace, size_t workspace_bytes,
+                         int B, int N, int M, void *stream) {
+    if (!cost || !value_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
+    if (B < 1 || N < 1 || M < 1) return fail(ALIGNER_EINVAL, "bad shape");
+    if (!(gamma > 0.f) || !(gamma < __builtin_huge_valf())) return fail(ALIGNER_EINVAL, "gamma must be positive and finite");
+    if (!(warp_penalty >= 0.f) || !(warp_penalty < __builtin_huge_valf()))
+        return fail(ALIGNER_EINVAL, "warp_penalty must be finite and not negative");
+    if (bandwidth < -1) return fail(ALIGNER_EINVAL, "bandwidth must be -1 (none) or at least 0");
+    if (B > 65535) return fail(ALIGNER_EDOM, "B=%d too large", B);
+    if (N > SD_MAX_N) return fail(ALIGNER_EDOM, "N=%d too large (<= %d)", N, SD_MAX_N);
+    if ((long long)N * M >= (1ll << 29)) return fail(ALIGNER_EDOM, "N*M=%lld too large (< 2^29)", (long long)N * M);
+    const size_t need = aligner_soft_dtw_workspace_bytes(B, N, M, grad_out != nullptr);
+    if (workspace_bytes < need)
+        return fail(ALIGNER_ENOSPC, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SoftDtwParams p;
+    p.cost = cost; p.ns = n_dev; p.ms = m_dev;
+    const double scale = 1.4426950408889634 / (double)gamma;
+    p.scale = (float)scale;
+    const double pen = (double)warp_penalty * scale;
+    p.pen = pen < (double)SD_BIG ? (float)pen : SD_BIG;
+    p.unscale = (float)((double)gamma * 0.6931471805599453);
+    p.band = (bandwidth < 0 || bandwidth > SD_NO_BAND) ? SD_NO_BAND : bandwidth;
+    p.value = value_out; p.grad = grad_out; p.fin = static_cast<float *>(workspace);
+    p.B = B; p.N = N; p.M = M;
+    const int NW = (N + 63) / 64;
+    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(softdtw_forward_kernel), sd_lds_bytes(NW, false)));
+    hipLaunchKernelGGL(softdtw_forward_kernel, dim3(B), dim3(64 * NW), sd_lds_bytes(NW, false), s, p);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    if (grad_out) {
+        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(softdtw_backward_kernel), sd_lds_bytes(NW, true)));
+        hipLaunchKernelGGL(softdtw_backward_kernel, dim3(B), dim3(64 * NW), sd_lds_bytes(NW, true), s, p);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    return ALIGNER_OK;
+}
+
+}  // extern "C"

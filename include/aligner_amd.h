@@ -45,7 +45,8 @@ extern "C" {
  *    log-likelihood front end -- aligner_gauss_logp / aligner_gauss_logp_workspace_bytes, its gradient
  *    aligner_gauss_logp_backward_f32 / aligner_gauss_logp_backward_workspace_bytes; and their likelihood loss on
  *    the hard path -- aligner_gauss_nll_f32 / aligner_gauss_nll_workspace_bytes; and Gaussian upsampling with its
- *    gradient -- aligner_gauss_upsample_f32 / aligner_gauss_upsample_backward_f32 and their *_workspace_bytes. */
+ *    gradient -- aligner_gauss_upsample_f32 / aligner_gauss_upsample_backward_f32 and their *_workspace_bytes; and
+ *    Soft-DTW with its expected alignment matrix -- aligner_soft_dtw_f32 / aligner_soft_dtw_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -762,6 +763,34 @@ int aligner_boundary_search_backward(const void *energies_dev, int energy_dtype,
                                      const float *grad_gamma_dev, float *grad_energies_out_dev,
                                      void *workspace_dev, size_t workspace_bytes,
                                      int B, int Tx, int Ty, void *stream);
+
+/*
+ * Soft-DTW (Cuturi & Blondel 2017) between two frame sequences, and its expected alignment matrix (Mensch & Blondel
+ * 2018): the loss Parallel Tacotron 2 trains on.  Build-defined (the reference snapshot has no such code).  For
+ * utterance b take D = the first n rows and m columns of cost[b], gamma > 0, a warp penalty p >= 0, a band w:
+ *
+ *     softmin_g(a,b,c) = -gamma log(exp(-a/gamma) + exp(-b/gamma) + exp(-c/gamma))
+ *     R[i,j] = D[i,j] + softmin_g(R[i-1,j-1], R[i-1,j] + p, R[i,j-1] + p)     R[-1,-1] = 0, every other border cell +inf
+ *     value  = R[n-1,m-1]            E[i,j] = d value / d D[i,j]
+ *
+ * Cell (i,j) exists iff |i - j| <= w (bandwidth -1: no band).  A +inf cost is a forbidden cell; an utterance without a
+ * finite path (|n - m| > w, a length below 1, +inf costs across every path) has value +inf and an all-zero E.  A NaN
+ * cost leaves that utterance's outputs undefined and no other's.  No gradient for gamma or p.
+ *   cost_dev      [B,N,M] fp32, last axis contiguous; n_dev / m_dev optional [B] int32 (null: N / M; clamped from above)
+ *   value_out_dev [B] fp32
+ *   grad_out_dev  optional [B,N,M] fp32: E, exactly 0 at and past n or m and outside the band.  Between the two
+ *                 launches it holds R: E overwrites it in place, so the call's peak memory is the two tensors.
+ *   ws_dev        aligner_soft_dtw_workspace_bytes(B,N,M,want_grad) bytes (0: shape outside the domain)
+ * One workgroup per utterance and no communication between workgroups; the same bits on every call.  Domain: N <= 1024,
+ * B <= 65535, N*M < 2^29: ALIGNER_EDOM beyond; ALIGNER_EINVAL for a null pointer, a shape below 1, a gamma that is
+ * not positive and finite, a penalty that is negative or not finite, a bandwidth below -1; ALIGNER_ENOSPC for a
+ * workspace that is too small.  Validated before any HIP call.  Asynchronous on the stream, capturable.
+ */
+size_t aligner_soft_dtw_workspace_bytes(int B, int N, int M, int want_grad);
+int aligner_soft_dtw_f32(const float *cost_dev, const int32_t *n_dev, const int32_t *m_dev,
+                         float gamma, float warp_penalty, int bandwidth,
+                         float *value_out_dev, float *grad_out_dev,
+                         void *ws_dev, size_t ws_bytes, int B, int N, int M, void *hip_stream);
 
 #ifdef __cplusplus
 }
