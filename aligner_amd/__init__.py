@@ -23,6 +23,7 @@ from .gausslogp import gaussian_align, gaussian_forward_sum_loss, gaussian_logp,
 from .gaussnll import gaussian_nll, gaussian_nll_loss  # noqa: F401
 from .gaussup import gaussian_upsample, gaussian_upsample_at  # noqa: F401
 from .softdtw import soft_dtw, soft_dtw_loss  # noqa: F401
+from .l1cost import l1_cost, l1_cost_backward, soft_dtw_l1_loss  # noqa: F401
 
 __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status",
            "soft_attention", "soft_attention_backward", "conv1d", "conv1d_backward", "alignment_encoder", "AlignmentEncoderParams",
@@ -31,6 +32,7 @@ __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status"
            "align_with_pauses", "PauseAlignment", "gaussian_logp", "gaussian_logp_backward", "gaussian_forward_sum_loss",
            "gaussian_align", "gaussian_nll", "gaussian_nll_loss",
            "gaussian_upsample", "gaussian_upsample_at", "soft_dtw", "soft_dtw_loss",
+           "l1_cost", "l1_cost_backward", "soft_dtw_l1_loss",
            "install_dropin"]
 
 

@@ -10,7 +10,8 @@ For utterance b take D = cost[b, :n[b], :m[b]], gamma > 0, a warp penalty p >= 0
 
 Cell (i,j) exists iff |i - j| <= w.  A +inf cost is a forbidden cell; an utterance without a finite path (|n - m| > w, a
 length below 1, +inf costs across every path) has value +inf and an all-zero E, the "no alignment" convention of
-forward_sum().  Building the cost is the caller's job: torch.cdist(pred, target, p=1) is differentiable.
+forward_sum().  The L1 cost comes from l1_cost() (l1cost.py), built only where cells exist; soft_dtw_l1_loss() is the
+two as one autograd function.  Any other cost is the caller's to build.
 """
 from __future__ import annotations
 

@@ -46,7 +46,8 @@ extern "C" {
  *    aligner_gauss_logp_backward_f32 / aligner_gauss_logp_backward_workspace_bytes; and their likelihood loss on
  *    the hard path -- aligner_gauss_nll_f32 / aligner_gauss_nll_workspace_bytes; and Gaussian upsampling with its
  *    gradient -- aligner_gauss_upsample_f32 / aligner_gauss_upsample_backward_f32 and their *_workspace_bytes; and
- *    Soft-DTW with its expected alignment matrix -- aligner_soft_dtw_f32 / aligner_soft_dtw_workspace_bytes. */
+ *    Soft-DTW with its expected alignment matrix -- aligner_soft_dtw_f32 / aligner_soft_dtw_workspace_bytes; and its
+ *    banded L1 cost table with the gradient -- aligner_l1_cost_f32 / aligner_l1_cost_backward_f32. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -791,6 +792,33 @@ int aligner_soft_dtw_f32(const float *cost_dev, const int32_t *n_dev, const int3
                          float gamma, float warp_penalty, int bandwidth,
                          float *value_out_dev, float *grad_out_dev,
                          void *ws_dev, size_t ws_bytes, int B, int N, int M, void *hip_stream);
+
+/*
+ * The L1 cost table Soft-DTW runs on, built where soft_dtw's cells exist, and its gradient.  Build-defined.  With
+ * n = n_dev[b], m = m_dev[b] (null: N / M; clamped to [0,N] / [0,M]) and the band w of aligner_soft_dtw_f32:
+ *
+ *     cost[b,i,j] = scale sum_c |pred[b,c,i] - target[b,c,j]|      i < n, j < m, |i - j| <= w     (an existing cell)
+ *                 = +inf                                           i < n, j < m, |i - j| >  w     (soft_dtw's forbidden cell)
+ *                 = 0                                              at or past n or m
+ *
+ *     dpred[b,c,i]   =  k sum_j G[b,i,j] sign(pred[b,c,i] - target[b,c,j])      k = scale row_scale[b], rounded once
+ *     dtarget[b,c,j] = -k sum_i G[b,i,j] sign(pred[b,c,i] - target[b,c,j])      (row_scale null: k = scale)
+ *
+ * summed over existing cells only, sign(0) = 0 (torch.cdist's subgradient), both 0 at and past the lengths.  G is
+ * never read as a value where no cell exists: a NaN there reaches nothing.  Every element of each output is written.
+ *   pred_dev [B,C,N], target_dev [B,C,M], cost_out_dev / grad_cost_dev [B,N,M], dpred_out_dev [B,C,N],
+ *   dtarget_out_dev [B,C,M] (either may be null, not both), row_scale_dev optional [B]: all fp32, contiguous.
+ * Sums run in fp32 in a fixed order, one owner per output element, no atomics: the same bits on every call.  Neither
+ * call needs a workspace.  Domain: B <= 65535, C <= 4096, N*M < 2^29 (no limit on N alone: that one is the DP's):
+ * ALIGNER_EDOM beyond; ALIGNER_EINVAL for a null pointer, a shape below 1, a scale that is not finite, a bandwidth
+ * below -1.  Validated before any HIP call.  Asynchronous on the stream, capturable.
+ */
+int aligner_l1_cost_f32(const float *pred_dev, const float *target_dev, const int32_t *n_dev, const int32_t *m_dev,
+                        int bandwidth, float scale, float *cost_out_dev, int B, int C, int N, int M, void *hip_stream);
+int aligner_l1_cost_backward_f32(const float *grad_cost_dev, const float *pred_dev, const float *target_dev,
+                                 const int32_t *n_dev, const int32_t *m_dev, int bandwidth, float scale,
+                                 const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
+                                 int B, int C, int N, int M, void *hip_stream);
 
 #ifdef __cplusplus
 }
