@@ -1244,7 +1244,7 @@ __global__ __launch_bounds__(256) void mobo_backtrack_kernel(MoboParams p, int R
 // a block-wide prefix sum of alpha_i and of alpha_{i-1} over the frames.
 __global__ __launch_bounds__(256) void mobo_gamma_kernel(const float *__restrict__ log_alpha, const int *__restrict__ t_xs,
                                                           const int *__restrict__ t_ys, float *__restrict__ gamma,
-                                                          int Tx, int Ty) {
+                                                          int Tx, int Ty, int D) {
     __shared__ float wsum[2][4];
     __shared__ float carry[2];
     const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1252,7 +1252,7 @@ __global__ __launch_bounds__(256) void mobo_gamma_kernel(const float *__restrict
     I = I > Tx ? Tx : I;
     J = J > Ty ? Ty : J;
     float *g = gamma + ((size_t)b * Tx + i) * Ty;
-    if (i >= I || I < 1 || J < I) {
+    if (i >= I || I < 1 || J < I || (long long)J > (long long)I * D) {      // (no segmentation: 0, not "before the first boundary")
         for (int y = tid; y < Ty; y += 256) g[y] = 0.f;
         return;
     }
@@ -1578,7 +1578,7 @@ int aligner_boundary_search(const void *energies, int energy_dtype, const int32_
         ALIGNER_HIP_CHECK(hipGetLastError());
     }
     if (gamma_out) {
-        hipLaunchKernelGGL(mobo_gamma_kernel, dim3(Tx, B), dim3(256), 0, s, log_alpha_out, t_xs, t_ys, gamma_out, Tx, Ty);
+        hipLaunchKernelGGL(mobo_gamma_kernel, dim3(Tx, B), dim3(256), 0, s, log_alpha_out, t_xs, t_ys, gamma_out, Tx, Ty, pl.D);
         ALIGNER_HIP_CHECK(hipGetLastError());
     }
     return ALIGNER_OK;

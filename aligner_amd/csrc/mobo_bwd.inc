@@ -581,7 +581,9 @@ __global__ __launch_bounds__(256) void mobo_bwd_grad_kernel(MoboBwdParams p) {
     int I = p.t_xs[b], J = p.t_ys[b];
     I = I > p.Tx ? p.Tx : I;
     J = J > p.Ty ? p.Ty : J;
-    const bool ok = I >= 1 && J >= I && (long long)J <= (long long)I * D && !p.failw[b];
+    bool ok = I >= 1 && J >= I && (long long)J <= (long long)I * D && !p.failw[b];
+    // masked frames that leave P(b_{I-1} = J) = 0 leave no segmentation either: no gradient, as for such lengths
+    ok = ok && p.log_alpha[((size_t)b * p.Tx + (I - 1)) * p.Ty + (J - 1)] > MB_FINITE;
     const size_t ro = ((size_t)b * p.Tx + i) * p.Ty;
     if (!ok || i >= I || y0 >= J) {
         for (int y = y0 + tid; y < y0 + MB_NCH && y < p.Ty; y += 256) p.grad[ro + y] = 0.f;

@@ -706,7 +706,13 @@ int aligner_pausepath(const void *value_dev, int value_dtype, int ld_value, cons
  * oracle/mobo_oracle.py and aligner_amd/csrc/mobo.hip).  Boundaries 0 = b_-1 < b_0 < ... < b_{t_x-1} = t_y,
  * token durations 1..max_duration, P(b_i = j | b_{i-1} = k) = softmax over the feasible j in (k, k+max_duration]
  * of energies[b,i,j-1].
- *   energies_dev   [B,Tx,Ty] of energy_dtype F32, BF16 or F16 (the alignment layout, mel axis contiguous)
+ *   energies_dev   [B,Tx,Ty] of energy_dtype F32, BF16 or F16 (the alignment layout, mel axis contiguous).  Domain: -inf
+ *                      and NaN are masked frames (no boundary there, log_alpha -inf, gradient 0; a NaN fails every "is it
+ *                      live" comparison of the kernels exactly as -inf does).  Finite energies must stay far below 2^24
+ *                      base-2 units in magnitude (|e| log2(e) << 1.6e7; anything at or below -1e7 of those units counts as
+ *                      log 0: MB_DEADF in mobo.hip) -- a per-token offset of a hundred nats is well inside, and changes no
+ *                      result beyond rounding (the model only sees a token's energies up to a shift).  +inf and larger
+ *                      finite values are outside the domain: results undefined.  tests/mobo_cases.py pins this domain.
  *   boundaries_out_dev [B,Tx] int32: b_i of the most probable boundary sequence (rows >= t_x: t_y); NULL (with
  *                      durations_out_dev and map_score_out_dev NULL as well) when only log_alpha / gamma are wanted
  *                      (masked energies that leave no boundary sequence are then not reported: log_alpha of the last
@@ -718,7 +724,8 @@ int aligner_pausepath(const void *value_dev, int value_dtype, int ld_value, cons
  *                      max_duration is an upper bound for every window), first 256 zeroed once (status word as for
  *                      aligner_maxpath: ALIGNER_ST_BAD_LENGTHS for an utterance without any segmentation -- not
  *                      t_x <= t_y <= t_x*max_duration, or masked (-inf) energies that leave no boundary sequence a
- *                      positive probability; its outputs are 0 / -inf).  It holds the normalisers
+ *                      positive probability; its boundaries / durations are 0 and its score -inf, and for such lengths
+ *                      log_alpha is -inf and gamma 0 everywhere).  It holds the normalisers
  *                      [B,Tx,Ty] fp32, the per-(token, position) durations [B,Tx,Ty+1] u16 and the ring through
  *                      which the position segments of an utterance hand their last max_duration entries on.
  * Only the chain that is asked for runs: the max-product one alone without log_alpha_out_dev (the MAP sequence: 0.47 ms at

@@ -49,6 +49,11 @@ def _bounds(I: int, J: int, D: int, i: int):
     return lo, hi
 
 
+def band(I: int, J: int, D: int, i: int):
+    """(lo_i, hi_i): the positions token i may end at (the definition above), for the tests' own restatements."""
+    return _bounds(I, J, D, i)
+
+
 def feasible(I: int, J: int, D: int) -> bool:
     return 1 <= I <= J <= I * D
 
@@ -128,6 +133,11 @@ def _lse_rows(w):
         with np.errstate(invalid="ignore"):
             out[ok] = m[ok] + np.log(np.exp(w[ok] - m[ok, None]).sum(axis=1))
     return out
+
+
+def lse_rows(w):
+    """_lse_rows under a public name (tests/mobo_cases.py builds its float64 rows from it)."""
+    return _lse_rows(w)
 
 
 def boundary_search_fast(e: np.ndarray, D: int):
@@ -280,13 +290,19 @@ def _forward_rows(e: np.ndarray, D: int):
 
 
 def boundary_search_backward(e: np.ndarray, D: int, grad_log_alpha=None, grad_gamma=None) -> np.ndarray:
-    """dl/de [I, J] for l = <grad_log_alpha, log_alpha> + <grad_gamma, gamma> (either may be None), float64."""
+    """dl/de [I, J] for l = <grad_log_alpha, log_alpha> + <grad_gamma, gamma> (either may be None), float64.
+
+    Convention, shared with the HIP path (include/aligner_amd.h): an utterance whose masked (-inf) energies leave no boundary
+    sequence a positive probability, log_alpha[I-1, J-1] = -inf, has no answer and therefore no gradient -- all zeros, not
+    the adjoint of the rows before the masked run."""
     from numpy.lib.stride_tricks import sliding_window_view as swv
     e = np.asarray(e, np.float64)
     I, J = e.shape
     if not feasible(I, J, D):
         raise ValueError(f"infeasible: need I <= J <= I*D (I={I}, J={J}, D={D})")
     la, Ls = _forward_rows(e, D)
+    if not np.isfinite(la[I, J]):
+        return np.zeros((I, J))
     G = np.zeros((I, J + 1))
     if grad_log_alpha is not None:
         g = np.asarray(grad_log_alpha, np.float64)
