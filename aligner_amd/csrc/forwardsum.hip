@@ -174,6 +174,205 @@ __device__ __forceinline__ void fs_bstore(float v, __amdgpu_buffer_rsrc_t r, uns
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
 }
 
+// What the hand-issued stagers below require of a launch: T_mel % 4 == 0, every tensor they touch 16-byte aligned, and
+// the utterance's block below 4 GiB (32-bit offsets).  Anything else takes fs_stager_scheduled.
+__host__ __device__ __forceinline__ bool fs_by_hand_ok(int Ty, int Tx, const void *a, const void *b, const void *c = nullptr) {
+    return Ty % 4 == 0 &&
+           ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0 &&
+           (size_t)Tx * Ty * sizeof(float) < (1ull << 32);
+}
+
+// ---- the dynamic LDS of every sweep kernel: ONE layout, from which the kernel takes its pointers (fs_lds) and the
+// launcher the size it asks for.  Arrays follow each other in the order of the members; the assert of each layout
+// checks that every array of doubles starts 8-byte aligned and every array moved in 16-byte accesses 16-byte aligned. ----
+// The one-wave kernels: tiles frame-major, [2][TW][ROWS] floats each (log-probs, [alpha,] alpha or gradient out), then
+// the per-frame rows [2][TW] of offsets (and of the CTC form's normalisers).
+template <int R, bool BACKWARD, bool CTC>
+struct FsOneWaveLds {
+    static constexpr int TW = (BACKWARD ? 64 : 128) / R, ROWS = 64 * R + 4;
+    static constexpr size_t tile = (size_t)2 * TW * ROWS * sizeof(float);
+    static constexpr size_t tlp = 0, tal = tile /* (backward only) */, tout = (BACKWARD ? 2 : 1) * tile, toff = tout + tile,
+                            tnrm = toff + 2 * TW * sizeof(double), bytes = tnrm + (CTC ? 2 * TW * sizeof(float) : 0);
+    static_assert(tal % 16 == 0 && tout % 16 == 0 && toff % 8 == 0 && (ROWS * sizeof(float)) % 16 == 0, "LDS alignment");
+};
+// The systolic forward kernels: [NW][2][64][TW + 4] log-probs and alpha (slot-major), [NW][2][TW] C_w per frame, [NW][2]
+// (C_w, drift) at the start of the tile, and between the two the CTC form's 64 partial sums of the normalisers.
+template <int SY_NW, int SY_TW, bool CTC>
+struct FsSysForwardLds {
+    static constexpr size_t tiles = (size_t)SY_NW * 2 * 64 * (SY_TW + 4) * sizeof(float);
+    static constexpr size_t tin = 0, tout = tiles, toff = 2 * tiles, tcg = toff + SY_NW * 2 * SY_TW * sizeof(double),
+                            tns = tcg + SY_NW * 2 * sizeof(double), tdr = tns + (CTC ? 64 * sizeof(double) : 0),
+                            bytes = tdr + SY_NW * 2 * sizeof(float);
+    static_assert(tout % 16 == 0 && toff % 8 == 0 && ((SY_TW + 4) * sizeof(float)) % 16 == 0, "LDS alignment");
+};
+// The systolic backward kernels, plain form: three tile arrays (log-probs, alpha, gradient out); [NW][2][TW] g of a wave's
+// first row (the ring the wave above reads, in quads) and [NW][64][4] where the other lanes write theirs; [NW][2][TW] C_w
+// and D_w per frame; [NW][2] (D_w, drift) at the start of the tile.
+template <int SY_NW, int SY_TW>
+struct FsSysBackwardLds {
+    static constexpr size_t tiles = (size_t)SY_NW * 2 * 64 * (SY_TW + 4) * sizeof(float);
+    static constexpr size_t tlp = 0, tal = tiles, tgr = 2 * tiles, tg = 3 * tiles, tgd = tg + SY_NW * 2 * SY_TW * sizeof(float),
+                            toff = tgd + SY_NW * 64 * 4 * sizeof(float), tdof = toff + SY_NW * 2 * SY_TW * sizeof(double),
+                            tdg = tdof + SY_NW * 2 * SY_TW * sizeof(double), tdr = tdg + SY_NW * 2 * sizeof(double),
+                            bytes = tdr + SY_NW * 2 * sizeof(float);
+    static_assert(tal % 16 == 0 && tgr % 16 == 0 && tg % 16 == 0 && tgd % 16 == 0 && toff % 8 == 0, "LDS alignment");
+};
+// ... and the CTC form: the ring holds (g_B, g_T) pairs, one frame at a time, and the frames' normalisers come along.
+template <int SY_NW, int SY_TW>
+struct FsSysCtcBackwardLds {
+    static constexpr size_t tiles = (size_t)SY_NW * 2 * 64 * (SY_TW + 4) * sizeof(float);
+    static constexpr size_t tlp = 0, tal = tiles, tgr = 2 * tiles, toff = 3 * tiles, tdof = toff + SY_NW * 2 * SY_TW * sizeof(double),
+                            tdg = tdof + SY_NW * 2 * SY_TW * sizeof(double), tg = tdg + SY_NW * 2 * sizeof(double),
+                            dump = tg + SY_NW * 2 * SY_TW * sizeof(float2), tnrm = dump + SY_NW * 64 * sizeof(float2),
+                            tdr = tnrm + SY_NW * 2 * SY_TW * sizeof(float), bytes = tdr + SY_NW * 2 * sizeof(float);
+    static_assert(tal % 16 == 0 && tgr % 16 == 0 && toff % 8 == 0 && tg % 8 == 0, "LDS alignment");
+};
+template <typename T> __device__ __forceinline__ T *fs_lds(float *smem, size_t off) {
+    return reinterpret_cast<T *>(reinterpret_cast<char *>(smem) + off);
+}
+
+// A tile's row of per-frame values (offsets, normalisers) between the workspace and LDS, one frame per thread `s`:
+// frames at or past t_y come in as zero and do not go out.
+template <typename T> __device__ __forceinline__ void fs_row_in(T *lds, const T *g, int s, int TW, int y0, int ty) {
+    if (s < TW) lds[s] = (y0 + s < ty) ? g[y0 + s] : T(0);
+}
+template <typename T> __device__ __forceinline__ void fs_row_out(T *g, const T *lds, int s, int TW, int y0, int ty) {
+    if (s < TW && y0 + s < ty) g[y0 + s] = lds[s];
+}
+
+// ---- the tile movers of the one-wave kernels: 192 stager threads (s = 0..191), tiles of TW frames x 64R rows, FRAME-major
+// in LDS at a row stride of ROWS = 64R + 4 floats ----
+// One tile of `ga` (and of `gb`: TWO) from the utterance's [Tx,Ty] blocks, frames y0.., into `da` (base-2 logs, fs_in) and
+// `db` (as it is).  Every load is unconditional (row and frame clamped into the utterance: the duplicates land in cells
+// the sweep overrides) -- a load behind a bounds test is compiled to "load, wait, select" and the tile would arrive one
+// element at a time -- and all loads come before all LDS writes: the whole tile in flight, one memory latency per tile.
+template <int R, int TW, bool TWO>
+__device__ __forceinline__ void fs_fm_stage(const float *ga, const float *gb, float *da, float *db, int s, int y0, int tx, int ty, int Ty) {
+    constexpr int ROWS = 64 * R + 4, NEL = TW * 64 * R, NIT = (NEL + FS_STAGERS - 1) / FS_STAGERS;
+    float v[NIT], w[NIT];
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+        int e = s + i * FS_STAGERS;
+        e = e < NEL ? e : NEL - 1;
+        const int r = e / TW, c = e - r * TW;
+        const int rc = r < tx ? r : tx - 1, yc = y0 + c < ty ? y0 + c : ty - 1;
+        v[i] = ga[(size_t)rc * Ty + yc];
+        if (TWO) w[i] = gb[(size_t)rc * Ty + yc];
+    }
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+        const int e = s + i * FS_STAGERS;
+        if (e < NEL) {
+            const int r = e / TW, c = e - r * TW;
+            da[c * ROWS + r] = fs_in(v[i]);
+            if (TWO) db[c * ROWS + r] = w[i];
+        }
+    }
+}
+// One frame-major tile from LDS to frames y0.. of the utterance's [Tx,Ty] block `g`.
+template <int R, int TW>
+__device__ __forceinline__ void fs_fm_store(float *g, const float *src, int s, int y0, int Tx, int Ty) {
+    constexpr int ROWS = 64 * R + 4;
+    for (int e = s; e < TW * 64 * R; e += FS_STAGERS) {
+        const int r = e / TW, c = e - r * TW;
+        if (r < Tx && y0 + c < Ty) g[(size_t)r * Ty + y0 + c] = src[c * ROWS + r];
+    }
+}
+
+// "No alignment" (t_x < 1 or t_x > t_y) leaves a forward kernel here: loss +inf, log Z -inf (thread `first`), and zeros
+// in `offs[t0], offs[t0 + step], ..` below NT.
+__device__ __forceinline__ void fs_no_alignment(const FwdSumParams &p, int b, bool first, double *offs, int t0, int step) {
+    if (first) { p.loss[b] = -FS_NEG_INF; p.logz[b] = (double)FS_NEG_INF; }
+    for (int t = t0; t < p.NT; t += step) offs[t] = 0.0;
+}
+// Frames from y_from on of the utterance's gradient block `g` (past its last tile; everything when no alignment
+// exists): 0.
+__device__ __forceinline__ void fs_zero_grad_from(float *g, int y_from, int Tx, int Ty, int tid, int nthreads) {
+    for (int r = 0; r < Tx; ++r)
+        for (int y = y_from + tid; y < Ty; y += nthreads) g[(size_t)r * Ty + y] = 0.f;
+}
+
+// ---- the tile movers of the systolic kernels: wave-sized tiles, SLOT-major in LDS ----
+// Slot r of a tile is text row 63 w + r - 1 forward (slot 0 is the ghost of the wave above) and 63 w + r backward (slot 63
+// is the ghost of the wave below).  A ghost slot is loaded but not stored: its row belongs to the neighbour.
+template <bool BACKWARD> __device__ __forceinline__ int fs_slot_row(int w, int r) { return BACKWARD ? 63 * w + r : 63 * w + r - 1; }
+template <bool BACKWARD> __device__ __forceinline__ bool fs_slot_owned(int r) { return BACKWARD ? r < 63 : r >= 1; }
+// the row a slot's loads read: clamped into the text (rows past it are staged as log 0 whatever was read; forward, the
+// ghost of wave 0 is row -1)
+template <bool BACKWARD> __device__ __forceinline__ int fs_row_clamp(int rs, int tx) {
+    return !BACKWARD && rs < 0 ? 0 : (rs < tx ? rs : tx - 1);
+}
+
+// The compiler-scheduled stager of one wave of the CTC kernels: the path of every call whose T_mel % 4 != 0 or whose
+// tensors are not 16-byte aligned (fs_by_hand_ok).  Element i of a lane is e = lane + 64 i of the tile: slot r = e / TW,
+// frame c = e - r TW.  ONE tile in flight, plain loads and stores: a phase cannot be shorter than a memory round trip,
+// whatever the sweepers do (two in flight, as the plain kernels have: DESIGN.md 5.1, open).  The plain kernels keep their own
+// loop (two register sets, whole tiles with buffer operations) in their bodies: as instantiations of this function
+// fwdsum_forward_sys_kernel<4, 16> lost a wave of occupancy and the side-by-side launch 2 % at T_mel % 4 != 0 (DESIGN.md
+// 5.1; tools/experiments/fwdsum_plain_shared_stager.patch has that form).
+//   WITH_ALPHA (backward, gradient-making): alpha, the wave's forward offsets C_w and the frames' normalisers come in with
+//       the scores; without it the tile's offsets (C_w forward, D_w backward) go OUT with the alpha or beta tile.
+// lp_g / al_g / out_g: the utterance's [Tx,Ty] blocks; offs_in / offs_out: this wave's per-frame offsets in the workspace;
+// nrm_g: the utterance's normalisers; tlp_w / tal_w / tout_w: this wave's two LDS tiles each; toffi_w / toffo_w / tnrm_w:
+// its two rows of per-frame values in LDS; `lag`: the phase this wave's first tile is due in.
+template <int SY_TW, bool BACKWARD, bool WITH_ALPHA>
+__device__ __forceinline__ void fs_stager_scheduled(const float *lp_g, const float *al_g, float *out_g, const double *offs_in,
+                                                    double *offs_out, const float *nrm_g, float *tlp_w, float *tal_w,
+                                                    const float *tout_w, double *toffi_w, const double *toffo_w, float *tnrm_w,
+                                                    int lag, int w, int lane, int tx, int ty, const FwdSumParams &p, int ntl, int nph) {
+    constexpr int PITCH = SY_TW + 4, SY_TILE = 64 * PITCH;
+    float v[SY_TW], u[SY_TW], n = 0.f;                        // the tile in flight: scores, alpha, ...
+    double o = 0.0;                                           // ... and this lane's frame of the offsets and normalisers
+    auto first_frame = [&](int k) { return (BACKWARD ? ntl - 1 - k : k) * SY_TW; };   // of the k-th tile in sweep order
+    auto issue = [&](int k) {                                 // unconditional loads (tile, row and frame clamped into the utterance)
+        const int y0 = first_frame(k < ntl ? k : ntl - 1);
+#pragma unroll
+        for (int i = 0; i < SY_TW; ++i) {
+            const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
+            const int rg = fs_row_clamp<BACKWARD>(fs_slot_row<BACKWARD>(w, r), tx), yc = y0 + c < ty ? y0 + c : ty - 1;
+            v[i] = lp_g[(size_t)rg * p.Ty + yc];
+            if (WITH_ALPHA) u[i] = al_g[(size_t)rg * p.Ty + yc];
+        }
+        if (WITH_ALPHA) {
+            const int yo = y0 + (lane & (SY_TW - 1)), yc = yo < ty ? yo : ty - 1;
+            o = offs_in[yc];
+            n = nrm_g[yc];
+        }
+    };
+    issue(0);
+    // (one loop over all phases: with the `lag` phases before the first tile as a loop of barriers ahead of it, the forward
+    // kernels took 27 and 21 more registers and lost a wave of occupancy each)
+    for (int ph = 0; ph < nph; ++ph) {
+        const int k = ph - lag, ks = ph - 2 - lag;            // the tile that comes in, the tile that goes out
+        if (k >= 0 && k < ntl) {
+            float *dlp = tlp_w + (k & 1) * SY_TILE, *dal = tal_w + (k & 1) * SY_TILE;
+#pragma unroll
+            for (int i = 0; i < SY_TW; ++i) {
+                const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
+                dlp[r * PITCH + c] = (fs_slot_row<BACKWARD>(w, r) < tx) ? fs_nat(v[i]) : FS_NEG_NAT;   // rows past the text: log 0
+                if (WITH_ALPHA) dal[r * PITCH + c] = u[i];
+            }
+            if (WITH_ALPHA && lane < SY_TW) {
+                const bool in = first_frame(k) + lane < ty;
+                toffi_w[(k & 1) * SY_TW + lane] = in ? o : 0.0;
+                tnrm_w[(k & 1) * SY_TW + lane] = in ? n : 0.f;
+            }
+            issue(k + 1);
+        }
+        if (ks >= 0 && ks < ntl) {
+            const float *src = tout_w + (ks & 1) * SY_TILE;
+            const int y0 = first_frame(ks);
+#pragma unroll
+            for (int i = 0; i < SY_TW; ++i) {
+                const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW, rs = fs_slot_row<BACKWARD>(w, r);
+                if (fs_slot_owned<BACKWARD>(r) && rs < p.Tx && y0 + c < p.Ty) out_g[(size_t)rs * p.Ty + y0 + c] = src[r * PITCH + c];
+            }
+            if (!WITH_ALPHA) fs_row_out(offs_out, toffo_w + (ks & 1) * SY_TW, lane, SY_TW, y0, ty);
+        }
+        lds_barrier();
+    }
+}
+
 // ---- a stager wave of the systolic kernels, with every global access issued by hand ----
 // Measured on the way here (fwdsum at [64,200,1000], 68 phases of ~3 300 cycles): neither the sweepers' instruction
 // count (halved: no change), nor the stagers' address arithmetic (removed: no change), nor their stores (removed: no
@@ -349,18 +548,18 @@ __device__ __forceinline__ void fs_grad_stager_by_hand(const float *lp_g, const 
         const int e4 = lane + 64 * j;
         rr[j] = e4 / QR;
         qd[j] = e4 - rr[j] * QR;
-        const int rs = 63 * w + rr[j];
-        const int rg = rs < tx ? rs : tx - 1;
+        const int rs = fs_slot_row<true>(w, rr[j]);
+        const int rg = fs_row_clamp<true>(rs, tx);
         const int qc = qd[j] < tailq ? qd[j] : tailq - 1;    // the last tile: quads past the tensor re-read the last one inside
         vo[j] = (unsigned)(((size_t)rg * Ty + 4 * qd[j]) * sizeof(float));
         vt[j] = (unsigned)(((size_t)rg * Ty + 4 * qc) * sizeof(float));
-        const bool sv = rr[j] < 63 && rs < Tx;
+        const bool sv = fs_slot_owned<true>(rr[j]) && rs < Tx;
         so[j] = (unsigned)(((size_t)(rs < Tx ? rs : 0) * Ty + 4 * qd[j]) * sizeof(float));
         mfull[j] = __builtin_amdgcn_ballot_w64(sv);
         mtail[j] = __builtin_amdgcn_ballot_w64(sv && qd[j] < tailq);
         rowok[j] = rs < tx;                                   // rows past the text are staged as log 0
     }
-    const bool allok = 63 * w + 63 < tx;                      // (uniform: most waves select nothing)
+    const bool allok = fs_slot_row<true>(w, 63) < tx;         // (uniform: most waves select nothing)
     const int fl = lane & (SY_TW - 1);                        // this lane's frame of a tile's offsets
     auto issue = [&](int k, fs_u32x4 (&sl)[NJ], fs_u32x4 (&sa)[NJ], unsigned long long &o) {
         const int t = ntl - 1 - (k < ntl ? k : ntl - 1);      // k-th tile from the end, clamped
@@ -429,20 +628,17 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_forward_kernel(FwdSumParams
     // tile: TW frames x 64R rows = 32 KB.  Frame-major in LDS with the row stride padded by 4 floats: the
     // sweeper's 16-byte accesses stay aligned and conflict-free, and the stagers' transposing accesses
     // (consecutive lanes = consecutive frames) spread over 8 banks instead of hitting one
-    constexpr int TW = 128 / R, ROWS = 64 * R + 4;
+    using L = FsOneWaveLds<R, false, false>;
+    constexpr int TW = L::TW, ROWS = L::ROWS;
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tin = fs_smem;                         // [2][TW][ROWS] log-probs, frame-major
-    float *tout = tin + 2 * TW * ROWS;            // [2][TW][ROWS] alpha
-    double *toff = reinterpret_cast<double *>(tout + 2 * TW * ROWS);   // [2][TW]
+    float *tin = fs_lds<float>(fs_smem, L::tlp);  // [2][TW][ROWS] log-probs, frame-major
+    float *tout = fs_lds<float>(fs_smem, L::tout);   // [2][TW][ROWS] alpha
+    double *toff = fs_lds<double>(fs_smem, L::toff); // [2][TW]
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
     FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
-    if (!(tx >= 1 && tx <= ty)) {                 // no monotonic alignment exists: loss = +inf
-        if (tid == 0) { p.loss[b] = -FS_NEG_INF; p.logz[b] = (double)FS_NEG_INF; }
-        for (int t = tid; t < p.NT; t += FS_THREADS) p.offs[(size_t)b * p.NT + t] = 0.0;
-        return;
-    }
+    if (!(tx >= 1 && tx <= ty)) return fs_no_alignment(p, b, tid == 0, p.offs + (size_t)b * p.NT, tid, FS_THREADS);
     const int ntl = (ty + TW - 1) / TW;
     float prev[R];
 #pragma unroll
@@ -453,39 +649,12 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_forward_kernel(FwdSumParams
     for (int ph = 0; ph < ntl + 2; ++ph) {
         if (!sweeper) {
             const int s = tid - 64;
-            if (ph < ntl) {
-                // Every load is unconditional (row and frame clamped into the utterance: the duplicates land
-                // in cells the sweep overrides) -- a load behind a bounds test is compiled to "load, wait,
-                // select" and the tile would arrive one element at a time.
-                float *dst = tin + (ph & 1) * TW * ROWS;
-                const int y0 = ph * TW;
-                constexpr int NEL = TW * 64 * R, NIT = (NEL + FS_STAGERS - 1) / FS_STAGERS;
-                constexpr int BATCH = NIT;               // the whole tile in flight: one memory latency per tile
-                for (int i0 = 0; i0 < NIT; i0 += BATCH) {
-                    float v[BATCH];
-#pragma unroll
-                    for (int i = 0; i < BATCH; ++i) {
-                        int e = s + (i0 + i) * FS_STAGERS;
-                        e = e < NEL ? e : NEL - 1;
-                        const int r = e / TW, c = e - r * TW;
-                        const int rc = r < tx ? r : tx - 1, yc = y0 + c < ty ? y0 + c : ty - 1;
-                        v[i] = p.logp[ubase + (size_t)rc * p.Ty + yc];
-                    }
-#pragma unroll
-                    for (int i = 0; i < BATCH; ++i) {
-                        const int e = s + (i0 + i) * FS_STAGERS;
-                        if (e < NEL) { const int r = e / TW, c = e - r * TW; dst[c * ROWS + r] = fs_in(v[i]); }
-                    }
-                }
-            }
+            if (ph < ntl)
+                fs_fm_stage<R, TW, false>(p.logp + ubase, nullptr, tin + (ph & 1) * TW * ROWS, nullptr, s, ph * TW, tx, ty, p.Ty);
             if (ph >= 2) {
-                const float *src = tout + (ph & 1) * TW * ROWS;
                 const int y0 = (ph - 2) * TW;
-                for (int e = s; e < TW * 64 * R; e += FS_STAGERS) {
-                    const int r = e / TW, c = e - r * TW;
-                    if (r < p.Tx && y0 + c < p.Ty) p.alpha[ubase + (size_t)r * p.Ty + y0 + c] = src[c * ROWS + r];
-                }
-                if (s < TW && y0 + s < ty) p.offs[(size_t)b * p.NT + y0 + s] = toff[(ph & 1) * TW + s];
+                fs_fm_store<R, TW>(p.alpha + ubase, tout + (ph & 1) * TW * ROWS, s, y0, p.Tx, p.Ty);
+                fs_row_out(p.offs + (size_t)b * p.NT, toff + (ph & 1) * TW, s, TW, y0, ty);
             }
         } else if (ph >= 1 && ph <= ntl) {
             const int t = ph - 1, y0 = t * TW;
@@ -548,12 +717,13 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_forward_kernel(FwdSumParams
 // ---- backward: beta on the fly, gradient = -posterior ----
 template <int R>
 __global__ __launch_bounds__(FS_THREADS) void fwdsum_backward_kernel(FwdSumParams p) {
-    constexpr int TW = 64 / R, ROWS = 64 * R + 4; // tile: TW frames x 64R rows = 16 KB (three operands, double-buffered)
+    using L = FsOneWaveLds<R, true, false>;
+    constexpr int TW = L::TW, ROWS = L::ROWS;     // tile: TW frames x 64R rows = 16 KB (three operands, double-buffered)
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tlp = fs_smem;                         // [2][TW][ROWS] log-probs
-    float *tal = tlp + 2 * TW * ROWS;             // [2][TW][ROWS] alpha (relative to C_y)
-    float *tgr = tal + 2 * TW * ROWS;             // [2][TW][ROWS] gradient out
-    double *toff = reinterpret_cast<double *>(tgr + 2 * TW * ROWS);    // [2][TW] C_y
+    float *tlp = fs_lds<float>(fs_smem, L::tlp);  // [2][TW][ROWS] log-probs
+    float *tal = fs_lds<float>(fs_smem, L::tal);  // [2][TW][ROWS] alpha (relative to C_y)
+    float *tgr = fs_lds<float>(fs_smem, L::tout); // [2][TW][ROWS] gradient out
+    double *toff = fs_lds<double>(fs_smem, L::toff);   // [2][TW] C_y
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
     FS_LENGTHS(p, b, tx, ty);
@@ -561,9 +731,7 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_backward_kernel(FwdSumParam
     const bool ok = tx >= 1 && tx <= ty && fs_has_alignment(logz);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     const int ntl = ok ? (ty + TW - 1) / TW : 0;
-    // frames past the utterance's last tile (everything when no alignment exists): gradient 0
-    for (int r = 0; r < p.Tx; ++r)
-        for (int y = ntl * TW + tid; y < p.Ty; y += FS_THREADS) p.grad[ubase + (size_t)r * p.Ty + y] = 0.f;
+    fs_zero_grad_from(p.grad + ubase, ntl * TW, p.Tx, p.Ty, tid, FS_THREADS);
     if (!ok) return;
     float g_prev[R];                              // beta[x,y+1] + logp[x,y+1], relative to D
 #pragma unroll
@@ -575,41 +743,12 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_backward_kernel(FwdSumParam
         if (!sweeper) {
             const int s = tid - 64;
             if (ph < ntl) {
-                const int t = ntl - 1 - ph, y0 = t * TW;
-                float *dlp = tlp + (ph & 1) * TW * ROWS, *dal = tal + (ph & 1) * TW * ROWS;
-                constexpr int NEL = TW * 64 * R, NIT = (NEL + FS_STAGERS - 1) / FS_STAGERS;
-                constexpr int BATCH = NIT;
-                for (int i0 = 0; i0 < NIT; i0 += BATCH) {
-                    float v[BATCH], w[BATCH];
-#pragma unroll
-                    for (int i = 0; i < BATCH; ++i) {
-                        int e = s + (i0 + i) * FS_STAGERS;
-                        e = e < NEL ? e : NEL - 1;
-                        const int r = e / TW, c = e - r * TW;
-                        const int rc = r < tx ? r : tx - 1, yc = y0 + c < ty ? y0 + c : ty - 1;
-                        v[i] = p.logp[ubase + (size_t)rc * p.Ty + yc];
-                        w[i] = p.alpha[ubase + (size_t)rc * p.Ty + yc];
-                    }
-#pragma unroll
-                    for (int i = 0; i < BATCH; ++i) {
-                        const int e = s + (i0 + i) * FS_STAGERS;
-                        if (e < NEL) {
-                            const int r = e / TW, c = e - r * TW;
-                            dlp[c * ROWS + r] = fs_in(v[i]);
-                            dal[c * ROWS + r] = w[i];
-                        }
-                    }
-                }
-                if (s < TW) toff[(ph & 1) * TW + s] = (y0 + s < ty) ? p.offs[(size_t)b * p.NT + y0 + s] : 0.0;
+                const int y0 = (ntl - 1 - ph) * TW;
+                fs_fm_stage<R, TW, true>(p.logp + ubase, p.alpha + ubase, tlp + (ph & 1) * TW * ROWS, tal + (ph & 1) * TW * ROWS, s,
+                                         y0, tx, ty, p.Ty);
+                fs_row_in(toff + (ph & 1) * TW, p.offs + (size_t)b * p.NT, s, TW, y0, ty);
             }
-            if (ph >= 2) {
-                const float *src = tgr + (ph & 1) * TW * ROWS;
-                const int y0 = (ntl - 1 - (ph - 2)) * TW;
-                for (int e = s; e < TW * 64 * R; e += FS_STAGERS) {
-                    const int r = e / TW, c = e - r * TW;
-                    if (r < p.Tx && y0 + c < p.Ty) p.grad[ubase + (size_t)r * p.Ty + y0 + c] = src[c * ROWS + r];
-                }
-            }
+            if (ph >= 2) fs_fm_store<R, TW>(p.grad + ubase, tgr + (ph & 1) * TW * ROWS, s, (ntl - 1 - (ph - 2)) * TW, p.Tx, p.Ty);
         } else if (ph >= 1 && ph <= ntl) {
             const int buf = (ph - 1) & 1, y0 = (ntl - 1 - (ph - 1)) * TW;
             const float *slp = tlp + buf * TW * ROWS + R * lane, *sal = tal + buf * TW * ROWS + R * lane;
@@ -692,15 +831,16 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
     // tiles are SLOT-major, a slot's TW frames contiguous and slots TW + 4 floats apart: every wave moves its tile with
     // 16-byte LDS accesses (a sweeper lane's operands are TW / 4 ds_read_b128, conflict-free at this pitch; frame-major,
     // they were 2 x TW ds_read_b32 and 850 of a phase's 3 200 cycles: tools/fwdsum_stamps.py)
+    using L = FsSysForwardLds<SY_NW, SY_TW, false>;
     constexpr int PITCH = SY_TW + 4, SY_TILE = 64 * PITCH;
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tin = fs_smem;                                     // [NW][2][64][PITCH] log-probs (slot = lane)
-    float *tout = tin + SY_NW * 2 * SY_TILE;                  // [NW][2][64][PITCH] alpha
-    double *toff = reinterpret_cast<double *>(tout + SY_NW * 2 * SY_TILE);   // [NW][2][TW] C_w per frame
+    float *tin = fs_lds<float>(fs_smem, L::tin);              // [NW][2][64][PITCH] log-probs (slot = lane)
+    float *tout = fs_lds<float>(fs_smem, L::tout);            // [NW][2][64][PITCH] alpha
+    double *toff = fs_lds<double>(fs_smem, L::toff);          // [NW][2][TW] C_w per frame
     constexpr int RB = SY_TW, NG = SY_TW / RB;                // frames between re-basings: once per tile (the rebasing
     // ladder is ~170 cycles of the sweeper's chain; fp32 holds the column near 0 over 16 frames as well as over 8)
-    double *tcg = toff + SY_NW * 2 * SY_TW;                   // [NW][2][NG] C_w at the start of each group ...
-    float *tdr = reinterpret_cast<float *>(tcg + SY_NW * 2 * NG);            // [NW][2][NG] ... and the group's drift
+    double *tcg = fs_lds<double>(fs_smem, L::tcg);            // [NW][2][NG] C_w at the start of each group ...
+    float *tdr = fs_lds<float>(fs_smem, L::tdr);              // [NW][2][NG] ... and the group's drift
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1);
@@ -708,19 +848,15 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
     FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     double *offs = p.offs + ((size_t)b * SY_NW_MAX + w) * p.NT;
-    if (!(tx >= 1 && tx <= ty)) {                             // no monotonic alignment exists: loss = +inf
-        if (tid == 0) { p.loss[b] = -FS_NEG_INF; p.logz[b] = (double)FS_NEG_INF; }
-        if (!sweeper) for (int t = lane; t < p.NT; t += 64) offs[t] = 0.0;
-        return;
-    }
+    // (the stager waves zero the offsets, each its sweeper's)
+    if (!(tx >= 1 && tx <= ty)) return fs_no_alignment(p, b, tid == 0, offs, sweeper ? p.NT : lane, 64);
     const int ntl = (ty + SY_TW - 1) / SY_TW;
     const int row = 63 * w + lane - 1;                        // sweeper: lane 0 is the ghost (row 63w-1)
     float prev = (w == 0 && lane == 0) ? 0.f : FS_NEG;        // row -1 is log 1 before the first frame
     const bool ghost = lane == 0;
     float drift = 0.f;
     // Two loops, one per role (same phase count): the stagers' tile in flight is then live in their loop only
-    const bool by_hand = p.Ty % 4 == 0 && ((reinterpret_cast<uintptr_t>(p.logp) | reinterpret_cast<uintptr_t>(p.alpha)) & 15) == 0 &&
-                         (size_t)p.Tx * p.Ty * sizeof(float) < (1ull << 32);
+    const bool by_hand = fs_by_hand_ok(p.Ty, p.Tx, p.logp, p.alpha);
     if (!sweeper && by_hand) {
         fs_stager_by_hand<SY_TW, false>(p.logp + ubase, p.alpha + ubase, offs, tin + w * 2 * SY_TILE, tout + w * 2 * SY_TILE,
                                         toff + w * 2 * SY_TW, w, w, lane, tx, ty, p.Tx, p.Ty, ntl, ntl + SY_NW + 1,
@@ -737,10 +873,9 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
 #pragma unroll
         for (int i = 0; i < SY_TW; ++i) {
             const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-            const int rs = 63 * w + r - 1;
-            const int rg = rs < 0 ? 0 : (rs < tx ? rs : tx - 1);
-            vo[i] = (unsigned)(((size_t)rg * p.Ty + c) * sizeof(float));
-            so[i] = (r >= 1 && rs < p.Tx) ? (unsigned)(((size_t)rs * p.Ty + c) * sizeof(float)) : FS_DROP;
+            const int rs = fs_slot_row<false>(w, r);
+            vo[i] = (unsigned)(((size_t)fs_row_clamp<false>(rs, tx) * p.Ty + c) * sizeof(float));
+            so[i] = (fs_slot_owned<false>(r) && rs < p.Tx) ? (unsigned)(((size_t)rs * p.Ty + c) * sizeof(float)) : FS_DROP;
         }
         auto stage_issue = [&](int tl, float (&v)[SY_TW]) {      // unconditional loads (row and frame clamped into the utterance)
             const int tc = tl < ntl ? tl : ntl - 1;
@@ -750,11 +885,10 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
                 for (int i = 0; i < SY_TW; ++i) v[i] = fs_bload(rs_in, vo[i], (unsigned)y0 * 4u);
                 return;
             }
-    #pragma unroll
+#pragma unroll
             for (int i = 0; i < SY_TW; ++i) {
                 const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;     // slot r, frame c
-                int rg = 63 * w + r - 1;
-                rg = rg < 0 ? 0 : (rg < tx ? rg : tx - 1);
+                const int rg = fs_row_clamp<false>(fs_slot_row<false>(w, r), tx);
                 const int yc = y0 + c < ty ? y0 + c : ty - 1;
                 v[i] = p.logp[ubase + (size_t)rg * p.Ty + yc];
             }
@@ -766,7 +900,7 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
 #pragma unroll
                 for (int i = 0; i < SY_TW; ++i) {
                     const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                    dst[r * PITCH + c] = (63 * w + r - 1 < tx) ? fs_nat(v[i]) : FS_NEG_NAT;   // rows past the text: log 0
+                    dst[r * PITCH + c] = (fs_slot_row<false>(w, r) < tx) ? fs_nat(v[i]) : FS_NEG_NAT;   // rows past the text: log 0
                 }
                 stage_issue(tl + 2, v);
             }
@@ -783,11 +917,11 @@ __device__ __forceinline__ void fwdsum_forward_sys_body(const FwdSumParams &p, c
 #pragma unroll
                     for (int i = 0; i < SY_TW; ++i) {
                         const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                        const int rg = 63 * w + r - 1;
-                        if (r >= 1 && rg < p.Tx && y0 + c < p.Ty) p.alpha[ubase + (size_t)rg * p.Ty + y0 + c] = src[r * PITCH + c];
+                        const int rg = fs_slot_row<false>(w, r);
+                        if (fs_slot_owned<false>(r) && rg < p.Tx && y0 + c < p.Ty) p.alpha[ubase + (size_t)rg * p.Ty + y0 + c] = src[r * PITCH + c];
                     }
                 }
-                if (lane < SY_TW && y0 + lane < ty) offs[y0 + lane] = toff[(w * 2 + (ts & 1)) * SY_TW + lane];
+                fs_row_out(offs, toff + (w * 2 + (ts & 1)) * SY_TW, lane, SY_TW, y0, ty);
             }
             lds_barrier();
         };
@@ -901,17 +1035,18 @@ template <int SY_NW, int SY_TW, bool BETA_ONLY, bool GRADHAND = false>
 __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, const int b) {
     constexpr int PITCH = SY_TW + 4, SY_TILE = 64 * PITCH, SY_THREADS = 2 * SY_NW * 64;   // slot-major tiles (see the forward kernel)
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tlp = fs_smem;                                     // [NW][2][64][PITCH] log-probs (slot = lane)
-    float *tal = tlp + SY_NW * 2 * SY_TILE;                   // alpha (relative to C_w)
-    float *tgr = tal + SY_NW * 2 * SY_TILE;                   // gradient out
-    float *tg = tgr + SY_NW * 2 * SY_TILE;                    // [NW][2][TW] g = beta + logp (relative to D_w) of a wave's FIRST row: feeds the wave above
-    float *tgd = tg + SY_NW * 2 * SY_TW;                      // [NW][64][4] where the other lanes write theirs
-    double *toff = reinterpret_cast<double *>(tgd + SY_NW * 64 * 4);       // [NW][2][TW] C_w per frame
-    double *tdof = toff + SY_NW * 2 * SY_TW;                  // [NW][2][TW] D_w per frame
+    using L = FsSysBackwardLds<SY_NW, SY_TW>;
+    float *tlp = fs_lds<float>(fs_smem, L::tlp);              // [NW][2][64][PITCH] log-probs (slot = lane)
+    float *tal = fs_lds<float>(fs_smem, L::tal);              // alpha (relative to C_w)
+    float *tgr = fs_lds<float>(fs_smem, L::tgr);              // gradient out
+    float *tg = fs_lds<float>(fs_smem, L::tg);                // [NW][2][TW] g = beta + logp (relative to D_w) of a wave's FIRST row: feeds the wave above
+    float *tgd = fs_lds<float>(fs_smem, L::tgd);              // [NW][64][4] where the other lanes write theirs
+    double *toff = fs_lds<double>(fs_smem, L::toff);          // [NW][2][TW] C_w per frame
+    double *tdof = fs_lds<double>(fs_smem, L::tdof);          // [NW][2][TW] D_w per frame
     constexpr int RB = SY_TW, NG = SY_TW / RB;                // frames between re-basings: once per tile (the rebasing
     // ladder is ~170 cycles of the sweeper's chain; fp32 holds the column near 0 over 16 frames as well as over 8)
-    double *tdg = tdof + SY_NW * 2 * SY_TW;                   // [NW][2][NG] D_w at the start of each group ...
-    float *tdr = reinterpret_cast<float *>(tdg + SY_NW * 2 * NG);            // [NW][2][NG] ... and the group's drift
+    double *tdg = fs_lds<double>(fs_smem, L::tdg);            // [NW][2][NG] D_w at the start of each group ...
+    float *tdr = fs_lds<float>(fs_smem, L::tdr);              // [NW][2][NG] ... and the group's drift
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1), wr = SY_NW - 1 - w;     // wave SY_NW-1 (the last rows) leads
@@ -925,9 +1060,7 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
     const int ntl = ok ? (ty + SY_TW - 1) / SY_TW : 0;
     // frames past the utterance's last tile (everything when no alignment exists): gradient 0
     // (BETA_ONLY: fwdsum_combine_kernel writes every element of the gradient)
-    if (!BETA_ONLY)
-        for (int r = 0; r < p.Tx; ++r)
-            for (int y = ntl * SY_TW + tid; y < p.Ty; y += SY_THREADS) p.grad[ubase + (size_t)r * p.Ty + y] = 0.f;
+    if (!BETA_ONLY) fs_zero_grad_from(p.grad + ubase, ntl * SY_TW, p.Tx, p.Ty, tid, SY_THREADS);
     if (!ok) return;
     const double *offs = p.offs + ((size_t)b * SY_NW_MAX + w) * p.NT;
     double *doffs = p.doffs + ((size_t)b * SY_NW_MAX + w) * p.NT;
@@ -937,9 +1070,7 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
     float drift = 0.f;
     // Two loops, one per role (the phase count is the same): written as one loop with the role tested inside, the
     // stagers' tile in flight was live through the sweepers' code as well and the kernel spilled (236 -> 493 us).
-    const bool by_hand = BETA_ONLY && p.Ty % 4 == 0 &&
-                         ((reinterpret_cast<uintptr_t>(p.logp) | reinterpret_cast<uintptr_t>(p.grad)) & 15) == 0 &&
-                         (size_t)p.Tx * p.Ty * sizeof(float) < (1ull << 32);
+    const bool by_hand = BETA_ONLY && fs_by_hand_ok(p.Ty, p.Tx, p.logp, p.grad);
     // GRADHAND (the host checked: T_mel % 4 == 0, 16-byte aligned tensors, 32-bit offsets): the gradient-making kernel
     // with the hand-issued stager and NOTHING of the compiler-scheduled one in it -- that one spills (9 registers), and
     // a kernel that spills must not have hand-issued loads in flight
@@ -963,10 +1094,9 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
 #pragma unroll
         for (int i = 0; i < SY_TW; ++i) {
             const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-            const int rs = 63 * w + r;
-            const int rg = rs < tx ? rs : tx - 1;
-            vo[i] = (unsigned)(((size_t)rg * p.Ty + c) * sizeof(float));
-            so[i] = (r < 63 && rs < p.Tx) ? (unsigned)(((size_t)rs * p.Ty + c) * sizeof(float)) : FS_DROP;
+            const int rs = fs_slot_row<true>(w, r);
+            vo[i] = (unsigned)(((size_t)fs_row_clamp<true>(rs, tx) * p.Ty + c) * sizeof(float));
+            so[i] = (fs_slot_owned<true>(r) && rs < p.Tx) ? (unsigned)(((size_t)rs * p.Ty + c) * sizeof(float)) : FS_DROP;
         }
         auto stage_issue = [&](int kl, Set &q) {              // tile counted from the end, clamped
             const int kc = kl < ntl ? kl : ntl - 1;
@@ -984,8 +1114,7 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
 #pragma unroll
             for (int i = 0; i < SY_TW; ++i) {
                 const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                int rg = 63 * w + r;
-                rg = rg < tx ? rg : tx - 1;
+                const int rg = fs_row_clamp<true>(fs_slot_row<true>(w, r), tx);
                 const int yc = y0 + c < ty ? y0 + c : ty - 1;
                 q.v[i] = p.logp[ubase + (size_t)rg * p.Ty + yc];
                 if (!BETA_ONLY) q.u[i] = p.alpha[ubase + (size_t)rg * p.Ty + yc];
@@ -1001,7 +1130,7 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
 #pragma unroll
                 for (int i = 0; i < SY_TW; ++i) {
                     const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                    dlp[r * PITCH + c] = (63 * w + r < tx) ? fs_nat(q.v[i]) : FS_NEG_NAT;     // rows past the text: log 0
+                    dlp[r * PITCH + c] = (fs_slot_row<true>(w, r) < tx) ? fs_nat(q.v[i]) : FS_NEG_NAT;     // rows past the text: log 0
                     if (!BETA_ONLY) dal[r * PITCH + c] = q.u[i];
                 }
                 if (!BETA_ONLY && lane < SY_TW) toff[(w * 2 + (kl & 1)) * SY_TW + lane] = (y0 + lane < ty) ? q.o : 0.0;
@@ -1020,8 +1149,8 @@ __device__ __forceinline__ void fwdsum_backward_sys_body(const FwdSumParams &p, 
 #pragma unroll
                     for (int i = 0; i < SY_TW; ++i) {
                         const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                        const int rg = 63 * w + r;
-                        if (r < 63 && rg < p.Tx && y0 + c < p.Ty) p.grad[ubase + (size_t)rg * p.Ty + y0 + c] = src[r * PITCH + c];
+                        const int rg = fs_slot_row<true>(w, r);
+                        if (fs_slot_owned<true>(r) && rg < p.Tx && y0 + c < p.Ty) p.grad[ubase + (size_t)rg * p.Ty + y0 + c] = src[r * PITCH + c];
                     }
                 }
                 if (BETA_ONLY && lane < SY_TW && y0 + lane < ty) doffs[y0 + lane] = tdof[(w * 2 + (ks & 1)) * SY_TW + lane];
@@ -1333,21 +1462,19 @@ __global__ __launch_bounds__(256) void ctc_colnorm_kernel(CtcParams q) {
 template <int R>
 __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_forward_kernel(CtcParams q) {
     const FwdSumParams &p = q.f;
-    constexpr int TW = 128 / R, ROWS = 64 * R + 4;
+    using L = FsOneWaveLds<R, false, true>;
+    constexpr int TW = L::TW, ROWS = L::ROWS;
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tin = fs_smem;                         // [2][TW][ROWS] scores, frame-major
-    float *tout = tin + 2 * TW * ROWS;            // [2][TW][ROWS] alpha of the token states
-    double *toff = reinterpret_cast<double *>(tout + 2 * TW * ROWS);   // [2][TW]
-    float *tnrm = reinterpret_cast<float *>(toff + 2 * TW);            // [2][TW] n_y
+    float *tin = fs_lds<float>(fs_smem, L::tlp);  // [2][TW][ROWS] scores, frame-major
+    float *tout = fs_lds<float>(fs_smem, L::tout);   // [2][TW][ROWS] alpha of the token states
+    double *toff = fs_lds<double>(fs_smem, L::toff); // [2][TW]
+    float *tnrm = fs_lds<float>(fs_smem, L::tnrm);   // [2][TW] n_y
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
     FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
-    if (!(tx >= 1 && tx <= ty)) {                 // fewer frames than tokens: no labelling exists, loss = +inf
-        if (tid == 0) { p.loss[b] = -FS_NEG_INF; p.logz[b] = (double)FS_NEG_INF; }
-        for (int t = tid; t < p.NT; t += FS_THREADS) p.offs[(size_t)b * p.NT + t] = 0.0;
-        return;
-    }
+    // (fewer frames than tokens: no labelling exists)
+    if (!(tx >= 1 && tx <= ty)) return fs_no_alignment(p, b, tid == 0, p.offs + (size_t)b * p.NT, tid, FS_THREADS);
     const int ntl = (ty + TW - 1) / TW;
     double pB[R], pT[R];
 #pragma unroll
@@ -1359,33 +1486,13 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_forward_kernel(CtcParam
         if (!sweeper) {
             const int s = tid - 64;
             if (ph < ntl) {
-                float *dst = tin + (ph & 1) * TW * ROWS;
-                const int y0 = ph * TW;
-                constexpr int NEL = TW * 64 * R, NIT = (NEL + FS_STAGERS - 1) / FS_STAGERS;
-                float v[NIT];
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    int e = s + i * FS_STAGERS;
-                    e = e < NEL ? e : NEL - 1;
-                    const int r = e / TW, c = e - r * TW;
-                    const int rc = r < tx ? r : tx - 1, yc = y0 + c < ty ? y0 + c : ty - 1;
-                    v[i] = p.logp[ubase + (size_t)rc * p.Ty + yc];
-                }
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    const int e = s + i * FS_STAGERS;
-                    if (e < NEL) { const int r = e / TW, c = e - r * TW; dst[c * ROWS + r] = fs_in(v[i]); }
-                }
-                if (s < TW) tnrm[(ph & 1) * TW + s] = (y0 + s < ty) ? q.nrm[(size_t)b * p.Ty + y0 + s] : 0.f;
+                fs_fm_stage<R, TW, false>(p.logp + ubase, nullptr, tin + (ph & 1) * TW * ROWS, nullptr, s, ph * TW, tx, ty, p.Ty);
+                fs_row_in(tnrm + (ph & 1) * TW, q.nrm + (size_t)b * p.Ty, s, TW, ph * TW, ty);
             }
             if (ph >= 2) {
-                const float *src = tout + (ph & 1) * TW * ROWS;
                 const int y0 = (ph - 2) * TW;
-                for (int e = s; e < TW * 64 * R; e += FS_STAGERS) {
-                    const int r = e / TW, c = e - r * TW;
-                    if (r < p.Tx && y0 + c < p.Ty) p.alpha[ubase + (size_t)r * p.Ty + y0 + c] = src[c * ROWS + r];
-                }
-                if (s < TW && y0 + s < ty) p.offs[(size_t)b * p.NT + y0 + s] = toff[(ph & 1) * TW + s];
+                fs_fm_store<R, TW>(p.alpha + ubase, tout + (ph & 1) * TW * ROWS, s, y0, p.Tx, p.Ty);
+                fs_row_out(p.offs + (size_t)b * p.NT, toff + (ph & 1) * TW, s, TW, y0, ty);
             }
         } else if (ph >= 1 && ph <= ntl) {
             const int t = ph - 1, y0 = t * TW;
@@ -1451,21 +1558,21 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_forward_kernel(CtcParam
 template <int R>
 __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_backward_kernel(CtcParams q) {
     const FwdSumParams &p = q.f;
-    constexpr int TW = 64 / R, ROWS = 64 * R + 4;
+    using L = FsOneWaveLds<R, true, true>;
+    constexpr int TW = L::TW, ROWS = L::ROWS;
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tlp = fs_smem;                         // [2][TW][ROWS] scores
-    float *tal = tlp + 2 * TW * ROWS;             // [2][TW][ROWS] alpha of the token states (relative to C_y)
-    float *tgr = tal + 2 * TW * ROWS;             // [2][TW][ROWS] gradient out
-    double *toff = reinterpret_cast<double *>(tgr + 2 * TW * ROWS);    // [2][TW] C_y
-    float *tnrm = reinterpret_cast<float *>(toff + 2 * TW);            // [2][TW] n_y
+    float *tlp = fs_lds<float>(fs_smem, L::tlp);  // [2][TW][ROWS] scores
+    float *tal = fs_lds<float>(fs_smem, L::tal);  // [2][TW][ROWS] alpha of the token states (relative to C_y)
+    float *tgr = fs_lds<float>(fs_smem, L::tout); // [2][TW][ROWS] gradient out
+    double *toff = fs_lds<double>(fs_smem, L::toff);   // [2][TW] C_y
+    float *tnrm = fs_lds<float>(fs_smem, L::tnrm);     // [2][TW] n_y
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const bool sweeper = tid < 64;
     FS_LENGTHS(p, b, tx, ty);
     const bool ok = tx >= 1 && tx <= ty;
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     const int ntl = ok ? (ty + TW - 1) / TW : 0;
-    for (int r = 0; r < p.Tx; ++r)
-        for (int y = ntl * TW + tid; y < p.Ty; y += FS_THREADS) p.grad[ubase + (size_t)r * p.Ty + y] = 0.f;
+    fs_zero_grad_from(p.grad + ubase, ntl * TW, p.Tx, p.Ty, tid, FS_THREADS);
     if (!ok) return;
     const double logz = p.logz[b];
     double gB[R], gT[R];                          // beta + emission of frame y+1, relative to D (float64: see fs_lae2d)
@@ -1477,41 +1584,13 @@ __global__ __launch_bounds__(FS_THREADS) void fwdsum_ctc_backward_kernel(CtcPara
         if (!sweeper) {
             const int s = tid - 64;
             if (ph < ntl) {
-                const int t = ntl - 1 - ph, y0 = t * TW;
-                float *dlp = tlp + (ph & 1) * TW * ROWS, *dal = tal + (ph & 1) * TW * ROWS;
-                constexpr int NEL = TW * 64 * R, NIT = (NEL + FS_STAGERS - 1) / FS_STAGERS;
-                float v[NIT], w[NIT];
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    int e = s + i * FS_STAGERS;
-                    e = e < NEL ? e : NEL - 1;
-                    const int r = e / TW, c = e - r * TW;
-                    const int rc = r < tx ? r : tx - 1, yc = y0 + c < ty ? y0 + c : ty - 1;
-                    v[i] = p.logp[ubase + (size_t)rc * p.Ty + yc];
-                    w[i] = p.alpha[ubase + (size_t)rc * p.Ty + yc];
-                }
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    const int e = s + i * FS_STAGERS;
-                    if (e < NEL) {
-                        const int r = e / TW, c = e - r * TW;
-                        dlp[c * ROWS + r] = fs_in(v[i]);
-                        dal[c * ROWS + r] = w[i];
-                    }
-                }
-                if (s < TW) {
-                    toff[(ph & 1) * TW + s] = (y0 + s < ty) ? p.offs[(size_t)b * p.NT + y0 + s] : 0.0;
-                    tnrm[(ph & 1) * TW + s] = (y0 + s < ty) ? q.nrm[(size_t)b * p.Ty + y0 + s] : 0.f;
-                }
+                const int y0 = (ntl - 1 - ph) * TW;
+                fs_fm_stage<R, TW, true>(p.logp + ubase, p.alpha + ubase, tlp + (ph & 1) * TW * ROWS, tal + (ph & 1) * TW * ROWS, s,
+                                         y0, tx, ty, p.Ty);
+                fs_row_in(toff + (ph & 1) * TW, p.offs + (size_t)b * p.NT, s, TW, y0, ty);
+                fs_row_in(tnrm + (ph & 1) * TW, q.nrm + (size_t)b * p.Ty, s, TW, y0, ty);
             }
-            if (ph >= 2) {
-                const float *src = tgr + (ph & 1) * TW * ROWS;
-                const int y0 = (ntl - 1 - (ph - 2)) * TW;
-                for (int e = s; e < TW * 64 * R; e += FS_STAGERS) {
-                    const int r = e / TW, c = e - r * TW;
-                    if (r < p.Tx && y0 + c < p.Ty) p.grad[ubase + (size_t)r * p.Ty + y0 + c] = src[c * ROWS + r];
-                }
-            }
+            if (ph >= 2) fs_fm_store<R, TW>(p.grad + ubase, tgr + (ph & 1) * TW * ROWS, s, (ntl - 1 - (ph - 2)) * TW, p.Tx, p.Ty);
         } else if (ph >= 1 && ph <= ntl) {
             const int buf = (ph - 1) & 1, y0 = (ntl - 1 - (ph - 1)) * TW;
             const float *slp = tlp + buf * TW * ROWS + R * lane, *sal = tal + buf * TW * ROWS + R * lane;
@@ -1595,12 +1674,13 @@ __device__ __forceinline__ void fwdsum_ctc_forward_sys_body(const CtcParams &q, 
     // it: everything fwdsum_forward_sys_body says; what differs is the frame's arithmetic)
     constexpr int PITCH = SY_TW + 4, SY_TILE = 64 * PITCH, RB = SY_TW;
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tin = fs_smem;                                     // [NW][2][64][PITCH] scores (slot = lane)
-    float *tout = tin + SY_NW * 2 * SY_TILE;                  // [NW][2][64][PITCH] alpha of the token states
-    double *toff = reinterpret_cast<double *>(tout + SY_NW * 2 * SY_TILE);   // [NW][2][TW] C_w per frame
-    double *tcg = toff + SY_NW * 2 * SY_TW;                   // [NW][2] C_w at the start of the tile ...
-    double *tns = tcg + SY_NW * 2;                            // [64] partial sums of the frames' normalisers
-    float *tdr = reinterpret_cast<float *>(tns + 64);         // [NW][2] ... and the tile's drift
+    using L = FsSysForwardLds<SY_NW, SY_TW, true>;
+    float *tin = fs_lds<float>(fs_smem, L::tin);              // [NW][2][64][PITCH] scores (slot = lane)
+    float *tout = fs_lds<float>(fs_smem, L::tout);            // [NW][2][64][PITCH] alpha of the token states
+    double *toff = fs_lds<double>(fs_smem, L::toff);          // [NW][2][TW] C_w per frame
+    double *tcg = fs_lds<double>(fs_smem, L::tcg);            // [NW][2] C_w at the start of the tile ...
+    double *tns = fs_lds<double>(fs_smem, L::tns);            // [64] partial sums of the frames' normalisers
+    float *tdr = fs_lds<float>(fs_smem, L::tdr);              // [NW][2] ... and the tile's drift
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1);
@@ -1608,11 +1688,8 @@ __device__ __forceinline__ void fwdsum_ctc_forward_sys_body(const CtcParams &q, 
     FS_LENGTHS(p, b, tx, ty);
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     double *offs = p.offs + ((size_t)b * SY_NW_MAX + w) * p.NT;
-    if (!(tx >= 1 && tx <= ty)) {                             // fewer frames than tokens: no labelling exists, loss = +inf
-        if (tid == 0) { p.loss[b] = -FS_NEG_INF; p.logz[b] = (double)FS_NEG_INF; }
-        if (!sweeper) for (int t = lane; t < p.NT; t += 64) offs[t] = 0.0;
-        return;
-    }
+    // (fewer frames than tokens: no labelling exists)
+    if (!(tx >= 1 && tx <= ty)) return fs_no_alignment(p, b, tid == 0, offs, sweeper ? p.NT : lane, 64);
     const int ntl = (ty + SY_TW - 1) / SY_TW, nph = ntl + SY_NW + 1;
     const int row = 63 * w + lane - 1;                        // sweeper: lane 0 is the ghost (row 63w-1)
     const bool ghost = lane == 0;
@@ -1622,52 +1699,13 @@ __device__ __forceinline__ void fwdsum_ctc_forward_sys_body(const CtcParams &q, 
             for (int y = lane; y < ty; y += 64) ns += (double)q.nrm[(size_t)b * p.Ty + y];
             tns[lane] = ns;
         }
-        const bool by_hand = p.Ty % 4 == 0 && ((reinterpret_cast<uintptr_t>(p.logp) | reinterpret_cast<uintptr_t>(p.alpha)) & 15) == 0 &&
-                             (size_t)p.Tx * p.Ty * sizeof(float) < (1ull << 32);
-        if (by_hand) {
+        if (fs_by_hand_ok(p.Ty, p.Tx, p.logp, p.alpha))
             fs_stager_by_hand<SY_TW, false>(p.logp + ubase, p.alpha + ubase, offs, tin + w * 2 * SY_TILE, tout + w * 2 * SY_TILE,
                                             toff + w * 2 * SY_TW, w, w, lane, tx, ty, p.Tx, p.Ty, ntl, nph);
-            return;
-        }
-        // any T_mel / alignment: one tile in flight, scheduled by the compiler (a phase is then a memory round trip)
-        float vnext[SY_TW];
-        auto stage_issue = [&](int tl) {
-            const int tc = tl < ntl ? tl : ntl - 1;
-            const int y0 = tc * SY_TW;
-#pragma unroll
-            for (int i = 0; i < SY_TW; ++i) {
-                const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;     // slot r, frame c
-                int rg = 63 * w + r - 1;
-                rg = rg < 0 ? 0 : (rg < tx ? rg : tx - 1);
-                const int yc = y0 + c < ty ? y0 + c : ty - 1;
-                vnext[i] = p.logp[ubase + (size_t)rg * p.Ty + yc];
-            }
-        };
-        stage_issue(0);
-        for (int ph = 0; ph < nph; ++ph) {
-            const int tl = ph - w, ts = ph - 2 - w;
-            if (tl >= 0 && tl < ntl) {
-                float *dst = tin + (w * 2 + (tl & 1)) * SY_TILE;
-#pragma unroll
-                for (int i = 0; i < SY_TW; ++i) {
-                    const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                    dst[r * PITCH + c] = (63 * w + r - 1 < tx) ? fs_nat(vnext[i]) : FS_NEG_NAT;   // rows past the text: log 0
-                }
-                stage_issue(tl + 1);
-            }
-            if (ts >= 0 && ts < ntl) {
-                const float *src = tout + (w * 2 + (ts & 1)) * SY_TILE;
-                const int y0 = ts * SY_TW;
-#pragma unroll
-                for (int i = 0; i < SY_TW; ++i) {
-                    const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                    const int rg = 63 * w + r - 1;
-                    if (r >= 1 && rg < p.Tx && y0 + c < p.Ty) p.alpha[ubase + (size_t)rg * p.Ty + y0 + c] = src[r * PITCH + c];
-                }
-                if (lane < SY_TW && y0 + lane < ty) offs[y0 + lane] = toff[(w * 2 + (ts & 1)) * SY_TW + lane];
-            }
-            lds_barrier();
-        }
+        else    // any T_mel / alignment: one tile in flight (a phase is then a memory round trip), plain loads and stores
+            fs_stager_scheduled<SY_TW, false, false>(p.logp + ubase, nullptr, p.alpha + ubase, nullptr, offs, nullptr,
+                                                     tin + w * 2 * SY_TILE, nullptr, tout + w * 2 * SY_TILE, nullptr,
+                                                     toff + w * 2 * SY_TW, nullptr, w, w, lane, tx, ty, p, ntl, nph);
         return;
     }
     // ---- sweepers.  A frame: L = lse(B, T of the row above) serves both states --
@@ -1768,16 +1806,17 @@ __device__ __forceinline__ void fwdsum_ctc_backward_sys_body(const CtcParams &q,
     const FwdSumParams &p = q.f;
     constexpr int PITCH = SY_TW + 4, SY_TILE = 64 * PITCH, SY_THREADS = 2 * SY_NW * 64, RB = SY_TW;
     extern __shared__ __attribute__((aligned(16))) float fs_smem[];
-    float *tlp = fs_smem;                                     // [NW][2][64][PITCH] scores (slot = lane)
-    float *tal = tlp + SY_NW * 2 * SY_TILE;                   // alpha of the token states (relative to C_w)
-    float *tgr = tal + SY_NW * 2 * SY_TILE;                   // gradient out
-    double *toff = reinterpret_cast<double *>(tgr + SY_NW * 2 * SY_TILE);   // [NW][2][TW] C_w per frame
-    double *tdof = toff + SY_NW * 2 * SY_TW;                  // [NW][2][TW] D_w per frame
-    double *tdg = tdof + SY_NW * 2 * SY_TW;                   // [NW][2] D_w at the start of the tile ...
-    float2 *tg = reinterpret_cast<float2 *>(tdg + SY_NW * 2); // [NW][2][TW] (g_B, g_T) of a wave's FIRST row
-    float2 *dump = tg + SY_NW * 2 * SY_TW;                    // [NW][64] where the other lanes write
-    float *tnrm = reinterpret_cast<float *>(dump + SY_NW * 64);            // [NW][2][TW] n_y
-    float *tdr = tnrm + SY_NW * 2 * SY_TW;                    // [NW][2] ... and the tile's drift
+    using L = FsSysCtcBackwardLds<SY_NW, SY_TW>;
+    float *tlp = fs_lds<float>(fs_smem, L::tlp);              // [NW][2][64][PITCH] scores (slot = lane)
+    float *tal = fs_lds<float>(fs_smem, L::tal);              // alpha of the token states (relative to C_w)
+    float *tgr = fs_lds<float>(fs_smem, L::tgr);              // gradient out
+    double *toff = fs_lds<double>(fs_smem, L::toff);          // [NW][2][TW] C_w per frame
+    double *tdof = fs_lds<double>(fs_smem, L::tdof);          // [NW][2][TW] D_w per frame
+    double *tdg = fs_lds<double>(fs_smem, L::tdg);            // [NW][2] D_w at the start of the tile ...
+    float2 *tg = fs_lds<float2>(fs_smem, L::tg);              // [NW][2][TW] (g_B, g_T) of a wave's FIRST row
+    float2 *dump = fs_lds<float2>(fs_smem, L::dump);          // [NW][64] where the other lanes write
+    float *tnrm = fs_lds<float>(fs_smem, L::tnrm);            // [NW][2][TW] n_y
+    float *tdr = fs_lds<float>(fs_smem, L::tdr);              // [NW][2] ... and the tile's drift
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wave & (SY_NW - 1), wr = SY_NW - 1 - w;     // wave SY_NW-1 (the last rows) leads
@@ -1786,9 +1825,7 @@ __device__ __forceinline__ void fwdsum_ctc_backward_sys_body(const CtcParams &q,
     const bool ok = tx >= 1 && tx <= ty;
     const size_t ubase = (size_t)b * p.Tx * p.Ty;
     const int ntl = ok ? (ty + SY_TW - 1) / SY_TW : 0, nph = ntl + SY_NW + 1;
-    if (!BETA_ONLY)
-        for (int r = 0; r < p.Tx; ++r)
-            for (int y = ntl * SY_TW + tid; y < p.Ty; y += SY_THREADS) p.grad[ubase + (size_t)r * p.Ty + y] = 0.f;
+    if (!BETA_ONLY) fs_zero_grad_from(p.grad + ubase, ntl * SY_TW, p.Tx, p.Ty, tid, SY_THREADS);
     if (!ok) return;
     const double logz = BETA_ONLY ? 0.0 : p.logz[b];
     const double *offs = p.offs + ((size_t)b * SY_NW_MAX + w) * p.NT;
@@ -1796,66 +1833,14 @@ __device__ __forceinline__ void fwdsum_ctc_backward_sys_body(const CtcParams &q,
     const int row = 63 * w + lane;                            // sweeper: lane 63 is the ghost (row 63w+63)
     const bool ghost = lane == 63;
     if (!sweeper) {
-        const bool by_hand = BETA_ONLY && p.Ty % 4 == 0 &&
-                             ((reinterpret_cast<uintptr_t>(p.logp) | reinterpret_cast<uintptr_t>(p.grad)) & 15) == 0 &&
-                             (size_t)p.Tx * p.Ty * sizeof(float) < (1ull << 32);
-        if (by_hand) {
+        if (BETA_ONLY && fs_by_hand_ok(p.Ty, p.Tx, p.logp, p.grad))
             fs_stager_by_hand<SY_TW, true>(p.logp + ubase, p.grad + ubase, doffs, tlp + w * 2 * SY_TILE, tgr + w * 2 * SY_TILE,
                                            tdof + w * 2 * SY_TW, wr, w, lane, tx, ty, p.Tx, p.Ty, ntl, nph);
-            return;
-        }
-        float vnext[SY_TW], unext[SY_TW];
-        double onext = 0.0;
-        float nnext = 0.f;
-        auto stage_issue = [&](int kl) {                      // tile counted from the end, clamped
-            const int kc = kl < ntl ? kl : ntl - 1;
-            const int y0 = (ntl - 1 - kc) * SY_TW;
-#pragma unroll
-            for (int i = 0; i < SY_TW; ++i) {
-                const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                int rg = 63 * w + r;
-                rg = rg < tx ? rg : tx - 1;
-                const int yc = y0 + c < ty ? y0 + c : ty - 1;
-                vnext[i] = p.logp[ubase + (size_t)rg * p.Ty + yc];
-                if (!BETA_ONLY) unext[i] = p.alpha[ubase + (size_t)rg * p.Ty + yc];
-            }
-            const int yo = y0 + (lane & (SY_TW - 1));
-            if (!BETA_ONLY) {
-                onext = offs[yo < ty ? yo : ty - 1];
-                nnext = q.nrm[(size_t)b * p.Ty + (yo < ty ? yo : ty - 1)];
-            }
-        };
-        stage_issue(0);
-        for (int ph = 0; ph < nph; ++ph) {
-            const int kl = ph - wr, ks = ph - 2 - wr;         // tile counted from the end
-            if (kl >= 0 && kl < ntl) {
-                const int t = ntl - 1 - kl, y0 = t * SY_TW;
-                float *dlp = tlp + (w * 2 + (kl & 1)) * SY_TILE, *dal = tal + (w * 2 + (kl & 1)) * SY_TILE;
-#pragma unroll
-                for (int i = 0; i < SY_TW; ++i) {
-                    const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                    dlp[r * PITCH + c] = (63 * w + r < tx) ? fs_nat(vnext[i]) : FS_NEG_NAT;   // rows past the text: log 0
-                    if (!BETA_ONLY) dal[r * PITCH + c] = unext[i];
-                }
-                if (!BETA_ONLY && lane < SY_TW) {
-                    toff[(w * 2 + (kl & 1)) * SY_TW + lane] = (y0 + lane < ty) ? onext : 0.0;
-                    tnrm[(w * 2 + (kl & 1)) * SY_TW + lane] = (y0 + lane < ty) ? nnext : 0.f;
-                }
-                stage_issue(kl + 1);
-            }
-            if (ks >= 0 && ks < ntl) {
-                const float *src = tgr + (w * 2 + (ks & 1)) * SY_TILE;
-                const int y0 = (ntl - 1 - ks) * SY_TW;
-#pragma unroll
-                for (int i = 0; i < SY_TW; ++i) {
-                    const int e = lane + 64 * i, r = e / SY_TW, c = e - r * SY_TW;
-                    const int rg = 63 * w + r;
-                    if (r < 63 && rg < p.Tx && y0 + c < p.Ty) p.grad[ubase + (size_t)rg * p.Ty + y0 + c] = src[r * PITCH + c];
-                }
-                if (BETA_ONLY && lane < SY_TW && y0 + lane < ty) doffs[y0 + lane] = tdof[(w * 2 + (ks & 1)) * SY_TW + lane];
-            }
-            lds_barrier();
-        }
+        else    // (one tile in flight, plain loads and stores: see the forward kernel)
+            fs_stager_scheduled<SY_TW, true, !BETA_ONLY>(
+                p.logp + ubase, p.alpha + ubase, p.grad + ubase, offs, doffs, q.nrm + (size_t)b * p.Ty, tlp + w * 2 * SY_TILE,
+                tal + w * 2 * SY_TILE, tgr + w * 2 * SY_TILE, toff + w * 2 * SY_TW, tdof + w * 2 * SY_TW, tnrm + w * 2 * SY_TW, wr, w,
+                lane, tx, ty, p, ntl, nph);
         return;
     }
     // ---- sweepers (no select per row: see the forward kernel; below row t_x every state stays log 0 by itself) ----
@@ -2016,22 +2001,27 @@ static FsLayout fs_layout(int B, int Tx, int Ty) {
     return L;
 }
 
+// One kernel with its dynamic LDS; and the sequence of every launcher below: the forward kernel, then the backward
+// kernel if the gradient is asked for, B workgroups each.
+template <typename P>
+static int fs_launch_one(void (*k)(P), unsigned blocks, int threads, size_t lds, hipStream_t s, const P &p) {
+    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(k), lds));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, s, p);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+template <typename P>
+static int fs_launch_pair(void (*kf)(P), size_t lds_f, void (*kb)(P), size_t lds_b, bool backward, int B, int threads, hipStream_t s,
+                          const P &p) {
+    const int rc = fs_launch_one(kf, B, threads, lds_f, s, p);
+    return rc != ALIGNER_OK || !backward ? rc : fs_launch_one(kb, B, threads, lds_b, s, p);
+}
+constexpr size_t fs_max(size_t a, size_t b) { return a > b ? a : b; }
+
 template <int R>
 static int fs_launch(const FwdSumParams &p, bool backward, hipStream_t s) {
-    constexpr int ROWS = 64 * R + 4;
-    const size_t lds_f = (size_t)4 * (128 / R) * ROWS * sizeof(float) + 2 * (128 / R) * sizeof(double);
-    const size_t lds_b = (size_t)6 * (64 / R) * ROWS * sizeof(float) + 2 * (64 / R) * sizeof(double);
-    auto kf = fwdsum_forward_kernel<R>;
-    auto kb = fwdsum_backward_kernel<R>;
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kf), lds_f));
-    hipLaunchKernelGGL(kf, dim3(p.B), dim3(FS_THREADS), lds_f, s, p);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    if (backward) {
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kb), lds_b));
-        hipLaunchKernelGGL(kb, dim3(p.B), dim3(FS_THREADS), lds_b, s, p);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
-    return ALIGNER_OK;
+    return fs_launch_pair(fwdsum_forward_kernel<R>, FsOneWaveLds<R, false, false>::bytes, fwdsum_backward_kernel<R>,
+                          FsOneWaveLds<R, true, false>::bytes, backward, p.B, FS_THREADS, s, p);
 }
 
 // Both sweeps in one launch pay while all 2B workgroups can be resident at once, one per CU (tools/fwdsum_batch_sweep.py at
@@ -2042,105 +2032,71 @@ static bool fs_side_by_side(int B) { return 2 * B <= device_cu_count(); }
 template <int SY_NW, int SY_TW>
 static int fs_launch_sys(const FwdSumParams &p, bool backward, hipStream_t s) {
     constexpr int SY_THREADS = 2 * SY_NW * 64;
-    constexpr size_t grp = (size_t)SY_NW * 2 * (SY_TW / FS_RB) * (sizeof(double) + sizeof(float));   // (offset, drift) per group
-    constexpr size_t tile = (size_t)64 * (SY_TW + 4) * sizeof(float);                                // slot-major, pitch TW + 4
-    const size_t lds_f = 2 * SY_NW * 2 * tile + (size_t)SY_NW * 2 * SY_TW * sizeof(double) + grp;
-    const size_t lds_b = 3 * SY_NW * 2 * tile + (size_t)SY_NW * (2 * SY_TW + 64 * 4) * sizeof(float) +
-                         (size_t)2 * SY_NW * 2 * SY_TW * sizeof(double) + grp;
-    auto kf = fwdsum_forward_sys_kernel<SY_NW, SY_TW>;
-    const bool gradhand = backward && p.Ty % 4 == 0 && !p.no_grad_stager &&
-                          ((reinterpret_cast<uintptr_t>(p.logp) | reinterpret_cast<uintptr_t>(p.grad) |
-                            reinterpret_cast<uintptr_t>(p.alpha)) & 15) == 0 &&
-                          (size_t)p.Tx * p.Ty * sizeof(float) < (1ull << 32);
-    auto kb = gradhand ? fwdsum_backward_sys_kernel<SY_NW, SY_TW, true> : fwdsum_backward_sys_kernel<SY_NW, SY_TW, false>;
+    constexpr size_t lds_f = FsSysForwardLds<SY_NW, SY_TW, false>::bytes, lds_b = FsSysBackwardLds<SY_NW, SY_TW>::bytes;
     // with the gradient, on a batch that leaves half the CUs idle: both sweeps in one launch, then the combining pass
     if (backward && g_opt_fwdsum_serial <= 0 && fs_side_by_side(p.B) && p.doffs) {
-        auto k2 = fwdsum_both_sys_kernel<SY_NW, SY_TW>;
-        const size_t lds = lds_f > lds_b ? lds_f : lds_b;
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(k2), lds));
-        hipLaunchKernelGGL(k2, dim3(2 * p.B), dim3(SY_THREADS), lds, s, p);
-        ALIGNER_HIP_CHECK(hipGetLastError());
+        const int rc = fs_launch_one(fwdsum_both_sys_kernel<SY_NW, SY_TW>, 2 * p.B, SY_THREADS, fs_max(lds_f, lds_b), s, p);
+        if (rc != ALIGNER_OK) return rc;
         hipLaunchKernelGGL(fwdsum_combine_kernel, dim3((p.Ty + 255) / 256, (p.Tx + 62) / 63, p.B), dim3(256), 0, s, p);
         ALIGNER_HIP_CHECK(hipGetLastError());
         return ALIGNER_OK;
     }
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kf), lds_f));
-    hipLaunchKernelGGL(kf, dim3(p.B), dim3(SY_THREADS), lds_f, s, p);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    if (backward) {
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kb), lds_b));
-        hipLaunchKernelGGL(kb, dim3(p.B), dim3(SY_THREADS), lds_b, s, p);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
-    return ALIGNER_OK;
+    const bool gradhand = backward && !p.no_grad_stager && fs_by_hand_ok(p.Ty, p.Tx, p.logp, p.grad, p.alpha);
+    return fs_launch_pair(fwdsum_forward_sys_kernel<SY_NW, SY_TW>, lds_f,
+                          gradhand ? fwdsum_backward_sys_kernel<SY_NW, SY_TW, true> : fwdsum_backward_sys_kernel<SY_NW, SY_TW, false>,
+                          lds_b, backward, p.B, SY_THREADS, s, p);
 }
 
 template <int R>
 static int fs_launch_ctc(const CtcParams &q, bool backward, hipStream_t s) {
-    constexpr int ROWS = 64 * R + 4;
-    const size_t lds_f = (size_t)4 * (128 / R) * ROWS * sizeof(float) + 2 * (128 / R) * (sizeof(double) + sizeof(float));
-    const size_t lds_b = (size_t)6 * (64 / R) * ROWS * sizeof(float) + 2 * (64 / R) * (sizeof(double) + sizeof(float));
     hipLaunchKernelGGL(ctc_colnorm_kernel, dim3((q.f.Ty + 63) / 64, q.f.B), dim3(256), 0, s, q);
     ALIGNER_HIP_CHECK(hipGetLastError());
-    auto kf = fwdsum_ctc_forward_kernel<R>;
-    auto kb = fwdsum_ctc_backward_kernel<R>;
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kf), lds_f));
-    hipLaunchKernelGGL(kf, dim3(q.f.B), dim3(FS_THREADS), lds_f, s, q);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    if (backward) {
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kb), lds_b));
-        hipLaunchKernelGGL(kb, dim3(q.f.B), dim3(FS_THREADS), lds_b, s, q);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
-    return ALIGNER_OK;
+    return fs_launch_pair(fwdsum_ctc_forward_kernel<R>, FsOneWaveLds<R, false, true>::bytes, fwdsum_ctc_backward_kernel<R>,
+                          FsOneWaveLds<R, true, true>::bytes, backward, q.f.B, FS_THREADS, s, q);
 }
 
 template <int SY_NW, int SY_TW>
 static int fs_launch_ctc_sys(const CtcParams &q, bool backward, hipStream_t s) {
     constexpr int SY_THREADS = 2 * SY_NW * 64;
-    constexpr size_t tile = (size_t)64 * (SY_TW + 4) * sizeof(float);                                // slot-major, pitch TW + 4
-    const size_t lds_f = 2 * SY_NW * 2 * tile + (size_t)SY_NW * 2 * SY_TW * sizeof(double) + (size_t)SY_NW * 2 * sizeof(double) +
-                         64 * sizeof(double) + (size_t)SY_NW * 2 * sizeof(float);
-    const size_t lds_b = 3 * SY_NW * 2 * tile + (size_t)2 * SY_NW * 2 * SY_TW * sizeof(double) + (size_t)SY_NW * 2 * sizeof(double) +
-                         (size_t)SY_NW * 2 * SY_TW * (sizeof(float2) + sizeof(float)) + (size_t)SY_NW * 64 * sizeof(float2) +
-                         (size_t)SY_NW * 2 * sizeof(float);
+    constexpr size_t lds_f = FsSysForwardLds<SY_NW, SY_TW, true>::bytes, lds_b = FsSysCtcBackwardLds<SY_NW, SY_TW>::bytes;
+    // (the normaliser workgroups of the fused launches borrow the first 2 KB: ctc_colnorm_body's two [4][64] arrays)
+    static_assert(lds_f >= 512 * sizeof(float), "the normaliser workgroups' LDS");
     auto kf = fwdsum_ctc_forward_sys_kernel<SY_NW, SY_TW>;
-    auto kb = fwdsum_ctc_backward_sys_kernel<SY_NW, SY_TW>;
+    CtcParams qf = q;
+    qf.fused_norm = 1;
+    const unsigned ncol = (unsigned)((q.f.Ty + 63) / 64) * (unsigned)q.f.B;         // normaliser workgroups, behind the sweeps
     if (backward && g_opt_fwdsum_serial <= 0 && fs_side_by_side(q.f.B) && q.f.doffs) {
-        auto k2 = fwdsum_ctc_both_sys_kernel<SY_NW, SY_TW>;
-        const size_t lds = lds_f > lds_b ? lds_f : lds_b;
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(k2), lds));
-        CtcParams qf = q;
-        qf.fused_norm = 1;
-        const unsigned ncol = (unsigned)((q.f.Ty + 63) / 64) * (unsigned)q.f.B;     // normaliser workgroups, behind the sweeps
-        hipLaunchKernelGGL(k2, dim3(2 * q.f.B + ncol), dim3(SY_THREADS), lds, s, qf);
-        ALIGNER_HIP_CHECK(hipGetLastError());
+        const int rc = fs_launch_one(fwdsum_ctc_both_sys_kernel<SY_NW, SY_TW>, 2 * q.f.B + ncol, SY_THREADS, fs_max(lds_f, lds_b), s, qf);
+        if (rc != ALIGNER_OK) return rc;
         hipLaunchKernelGGL(fwdsum_ctc_combine_kernel, dim3((q.f.Ty + 255) / 256, (q.f.Tx + 62) / 63, q.f.B), dim3(256), 0, s, qf);
         ALIGNER_HIP_CHECK(hipGetLastError());
         return ALIGNER_OK;
     }
     if (!backward && g_opt_fwdsum_serial <= 0) {
         // the loss alone: the normalisers from extra workgroups of the sweep's launch, the loss finished behind it
-        CtcParams qf = q;
-        qf.fused_norm = 1;
-        const unsigned ncol = (unsigned)((q.f.Ty + 63) / 64) * (unsigned)q.f.B;
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kf), lds_f));
-        hipLaunchKernelGGL(kf, dim3(q.f.B + ncol), dim3(SY_THREADS), lds_f, s, qf);
-        ALIGNER_HIP_CHECK(hipGetLastError());
+        const int rc = fs_launch_one(kf, q.f.B + ncol, SY_THREADS, lds_f, s, qf);
+        if (rc != ALIGNER_OK) return rc;
         hipLaunchKernelGGL(fwdsum_ctc_loss_kernel, dim3(q.f.B), dim3(256), 0, s, qf);
         ALIGNER_HIP_CHECK(hipGetLastError());
         return ALIGNER_OK;
     }
     hipLaunchKernelGGL(ctc_colnorm_kernel, dim3((q.f.Ty + 63) / 64, q.f.B), dim3(256), 0, s, q);
     ALIGNER_HIP_CHECK(hipGetLastError());
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kf), lds_f));
-    hipLaunchKernelGGL(kf, dim3(q.f.B), dim3(SY_THREADS), lds_f, s, q);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    if (backward) {
-        ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kb), lds_b));
-        hipLaunchKernelGGL(kb, dim3(q.f.B), dim3(SY_THREADS), lds_b, s, q);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
+    return fs_launch_pair(kf, lds_f, fwdsum_ctc_backward_sys_kernel<SY_NW, SY_TW>, lds_b, backward, q.f.B, SY_THREADS, s, q);
+}
+
+// What the two entry points check alike, in the order they always did: pointers, shape, the form's row limit, (CTC) the
+// blank score and the grid, the workspace.  B == 0 passes: the caller returns before it launches.
+static int fs_check_args(const void *x, const int32_t *t_xs, const int32_t *t_ys, const float *loss_out, const void *workspace,
+                         size_t workspace_bytes, size_t need, int B, int Tx, int Ty, int max_tx, const char *max_tx_why, float blank,
+                         int max_B) {
+    if (!x || !t_xs || !t_ys || !loss_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
+    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (Tx > max_tx) return fail(ALIGNER_EDOM, "Tx=%d exceeds %d text rows%s", Tx, max_tx, max_tx_why);
+    if (!(blank - blank == 0.0f)) return fail(ALIGNER_EINVAL, "blank_logprob must be finite");
+    if (B == 0) return ALIGNER_OK;
+    if (B > max_B) return fail(ALIGNER_EDOM, "grid too large");
+    if (workspace_bytes < need) return fail(ALIGNER_ENOSPC, "workspace %zu < %zu bytes", workspace_bytes, need);
     return ALIGNER_OK;
 }
 
@@ -2158,12 +2114,9 @@ size_t aligner_forward_sum_workspace_bytes(int B, int Tx, int Ty) {
 int aligner_forward_sum_f32(const float *logp, const int32_t *t_xs, const int32_t *t_ys, float *loss_out,
                             float *grad_out, void *workspace, size_t workspace_bytes, int B, int Tx, int Ty,
                             void *stream) {
-    if (!logp || !t_xs || !t_ys || !loss_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
-    if (Tx > 1024) return fail(ALIGNER_EDOM, "Tx=%d exceeds 1024 text rows", Tx);
-    if (B == 0) return ALIGNER_OK;
-    const FsLayout L = fs_layout(B, Tx, Ty);
-    if (workspace_bytes < L.total) return fail(ALIGNER_ENOSPC, "workspace %zu < %zu bytes", workspace_bytes, L.total);
+    const FsLayout L = fs_layout(B, Tx > 0 ? Tx : 1, Ty > 0 ? Ty : 1);
+    const int rc = fs_check_args(logp, t_xs, t_ys, loss_out, workspace, workspace_bytes, L.total, B, Tx, Ty, 1024, "", 0.f, INT32_MAX);
+    if (rc != ALIGNER_OK || B == 0) return rc;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     FwdSumParams p{logp, t_xs, t_ys, reinterpret_cast<float *>(ws + L.alpha_off),
                    reinterpret_cast<double *>(ws + L.offs_off), reinterpret_cast<double *>(ws + L.logz_off),
@@ -2187,15 +2140,11 @@ size_t aligner_forward_sum_ctc_workspace_bytes(int B, int Tx, int Ty) {
 int aligner_forward_sum_ctc_f32(const float *scores, const int32_t *t_xs, const int32_t *t_ys, float blank_logprob,
                                 float *loss_out, float *grad_out, void *workspace, size_t workspace_bytes, int B, int Tx,
                                 int Ty, void *stream) {
-    if (!scores || !t_xs || !t_ys || !loss_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
-    if (Tx > 1023) return fail(ALIGNER_EDOM, "Tx=%d exceeds 1023 text rows (the blank after the last token takes a row)", Tx);
-    if (!(blank_logprob - blank_logprob == 0.0f)) return fail(ALIGNER_EINVAL, "blank_logprob must be finite");
-    if (B == 0) return ALIGNER_OK;
-    if (B > 65535) return fail(ALIGNER_EDOM, "grid too large");
-    const FsLayout L = fs_layout(B, Tx, Ty);
-    const size_t total = L.total + align_up((size_t)B * Ty * sizeof(float), 256);
-    if (workspace_bytes < total) return fail(ALIGNER_ENOSPC, "workspace %zu < %zu bytes", workspace_bytes, total);
+    const FsLayout L = fs_layout(B, Tx > 0 ? Tx : 1, Ty > 0 ? Ty : 1);
+    const size_t total = L.total + align_up((size_t)(B > 0 ? B : 0) * (Ty > 0 ? Ty : 1) * sizeof(float), 256);
+    const int rc = fs_check_args(scores, t_xs, t_ys, loss_out, workspace, workspace_bytes, total, B, Tx, Ty, 1023,
+                                 " (the blank after the last token takes a row)", blank_logprob, 65535);
+    if (rc != ALIGNER_OK || B == 0) return rc;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     CtcParams q{{scores, t_xs, t_ys, reinterpret_cast<float *>(ws + L.alpha_off), reinterpret_cast<double *>(ws + L.offs_off),
                  reinterpret_cast<double *>(ws + L.logz_off), loss_out, grad_out, B, Tx, Ty, L.NT,

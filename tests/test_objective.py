@@ -377,6 +377,37 @@ def test_gradient_stager_by_hand(dev, request, B, Tx, Ty):
         assert not grad_h[b, int(tx[b]):].any() and not grad_h[b, :, int(ty[b]):].any()
 
 
+# The hand-issued stagers and the compiler-scheduled one (fs_stager_scheduled: every call whose log-probs are not 16-byte
+# aligned) put the same values into LDS, and the sweepers mask the frames at or past t_y, where the two read different
+# cells: the same log-probs at an aligned address and 4 bytes into a larger buffer must give the same loss and gradient BIT
+# FOR BIT -- plain and CTC form, both sweeps in one launch and one after the other (`fwdsum_serial`), four waves with
+# 16-frame tiles and eight waves with 8-frame tiles.  Lengths: full extent (t_x > t_y: no alignment), all frames, and a t_y
+# that is no multiple of a tile width.
+@gpu
+@pytest.mark.parametrize("serial", [0, 1])
+@pytest.mark.parametrize("blank", [None, -1.0])
+@pytest.mark.parametrize("B,Tx,Ty,tx,ty", [(3, 70, 48, [70, 40, 33], [48, 48, 43]), (3, 260, 40, [260, 40, 17], [40, 40, 37])])
+def test_forward_sum_stagers_agree_bit_for_bit(dev, request, B, Tx, Ty, tx, ty, blank, serial):
+    import aligner_amd
+    from aligner_amd import _lib
+    rng = np.random.default_rng(5 * Tx + Ty)
+    lp = torch.from_numpy(_rand_logp(rng, B, Tx, Ty)).to(dev)
+    buf = torch.empty(B * Tx * Ty + 1, dtype=torch.float32, device=dev)
+    off = buf[1:].view(B, Tx, Ty)
+    off.copy_(lp)
+    assert lp.data_ptr() % 16 == 0 and off.data_ptr() % 16 == 4 and off.is_contiguous()
+    tx, ty = torch.tensor(tx, dtype=torch.int32), torch.tensor(ty, dtype=torch.int32)
+    lib = _lib.load()
+    request.addfinalizer(lambda: lib.aligner_debug_set_option(b"fwdsum_serial", 0))
+    _lib.check(lib.aligner_debug_set_option(b"fwdsum_serial", serial))
+    loss_a, grad_a = aligner_amd.forward_sum(lp, tx, ty, blank_logprob=blank)
+    loss_o, grad_o = aligner_amd.forward_sum(off, tx, ty, blank_logprob=blank)
+    torch.cuda.synchronize()
+    assert torch.isinf(loss_a[0]) and bool(torch.isfinite(loss_a[1:]).all()) and bool(grad_a[1:].any())
+    assert torch.equal(loss_a.view(torch.int32), loss_o.view(torch.int32))
+    assert torch.equal(grad_a.view(torch.int32), grad_o.view(torch.int32))
+
+
 # The systolic kernels' stagers issue 16-byte global accesses by hand when T_mel % 4 == 0 and the tensors are 16-byte
 # aligned; anything else takes the compiler-scheduled stager.  A log-prob tensor that starts 4 bytes into its buffer must
 # give the same numbers (and no misaligned access).
