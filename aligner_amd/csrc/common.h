@@ -57,6 +57,7 @@ extern unsigned long long *g_debug_stamps;
     X(maxpath_no_mask_verify, 0, "A-B / testing, a strict mask is always multiplied in (no verification pass)") \
     X(maxpath_zero_blocks, 0, "development, zero workgroups of the two-workgroup search launch (0: all idle CUs)") \
     X(maxpath_no_split_walk, 0, "A-B / testing, the two-workgroup search with one walker (the second half) for all rows") \
+    X(maxpath_log_launch, 0, "development, every launch of the search and of the expand entry point as one line on stderr: kernel, grid, block, LDS, MaxpathParams (tools/maxpath_launches.py)") \
     X(conv_no_fuse, 0, "testing / A-B, a stack's trailing narrow layers as separate kernels instead of conv_narrow_fused_kernel") \
     X(conv_split_always, env_flag("ALIGNER_CONV_SPLIT_ALWAYS"), "narrow layers never stage fp32 themselves (A/B, tests)") \
     X(softattn_split, 0, "development, waves per strip of the row-group form (2, 4; 1: at most 2; 0: the launch's choice)") \

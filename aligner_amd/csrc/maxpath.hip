@@ -1702,8 +1702,6 @@ static WsLayout ws_layout(int B, int Tx, int Ty) {
     return L;
 }
 
-static int lds_limit() { return device_lds_limit(); }
-
 static size_t starts_bytes(int Tx) { return (size_t)(((Tx + 1 + 63) / 64) * 64 + 64) * 4; }
 
 // Backtrack overlay size for a window of WT tiles (decision words in global memory).
@@ -1716,42 +1714,64 @@ static int pick_window(int NT, int ROWS, int Tx, size_t budget) {
     return walk_bytes(WT, ROWS, Tx) <= budget ? WT : 0;
 }
 
-template <typename K>
-static int launch_with_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, MaxpathParams p) {
-    p.lds_total = (int)lds;
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), lds));
-    hipLaunchKernelGGL(kernel, grid, block, lds, s, p);
-    ALIGNER_HIP_CHECK(hipGetLastError());
+static int check_shape(int B, int Tx, int Ty) {
+    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
     return ALIGNER_OK;
 }
 
-template <int NW, int DEPTH, bool VEC, int VT>
-static int launch_pipelined_mm(MaxpathParams p, int maskmode, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    if (maskmode == 0) return launch_with_lds(maxpath_pipelined_kernel<NW, DEPTH, VEC, 0, VT>, grid, block, lds, s, p);
-    if (NW <= 4) {
-        constexpr int N4 = NW <= 4 ? NW : 4;
-        if (maskmode == 2) return launch_with_lds(maxpath_pipelined_kernel<N4, DEPTH, VEC, 2, VT>, grid, block, lds, s, p);
-        return launch_with_lds(maxpath_pipelined_kernel<N4, DEPTH, VEC, 1, VT>, grid, block, lds, s, p);
+// Path dtype -> element type and a 1 in it (the 16-bit floats travel as their bits): f(one) with `one` of that type
+template <typename F>
+static int with_path_one(int path_dtype, F &&f) {
+    switch (path_dtype) {
+        case ALIGNER_DT_F32: return f(1.0f);
+        case ALIGNER_DT_F64: return f(1.0);
+        case ALIGNER_DT_I32: return f((int32_t)1);
+        case ALIGNER_DT_I64: return f((int64_t)1);
+        case ALIGNER_DT_U8:  return f((uint8_t)1);
+        case ALIGNER_DT_F16: return f((uint16_t)0x3C00);
+        case ALIGNER_DT_BF16: return f((uint16_t)0x3F80);
+        default: return fail(ALIGNER_EINVAL, "path dtype %d not supported", path_dtype);
     }
-    // eight waves (128 registers a lane) with the mask stream: one tile in flight per loader (with two the loaders' 2 x 2 x 16
-    // registers spilled: 30-41 VGPRs, 104-116 bytes of scratch a lane)
-    return launch_with_lds(maxpath_pipelined_kernel<NW, 1, VEC, 1, VT>, grid, block, lds, s, p);
 }
 
-template <int NW, int DEPTH>
-static int launch_pipelined(MaxpathParams p, bool vec, int maskmode, int vt, size_t lds, hipStream_t s) {
-    dim3 grid(p.B + p.zero_blocks), block(NW * 128);
-    if (vt != VT_F32) {
-        // 16-bit scores: 16-byte loaders only (the caller routes everything else to the generic kernel),
-        // and only the two wide workgroup shapes are built (narrow text runs on NW = 4 with idle waves)
-        if (NW >= 4) {
-            if (vt == VT_BF16) return launch_pipelined_mm<(NW >= 4 ? NW : 4), DEPTH, true, VT_BF16>(p, maskmode, grid, block, lds, s);
-            return launch_pipelined_mm<(NW >= 4 ? NW : 4), DEPTH, true, VT_F16>(p, maskmode, grid, block, lds, s);
-        }
-        return fail(ALIGNER_EINVAL, "internal: 16-bit scores on a narrow workgroup");
+// --------------------------------------------------------------------------
+// "maxpath_log_launch" (aligner_debug_set_option): every launch of the search (forward_impl) and of the expand entry
+// point as one line on stderr -- the kernel with its template arguments, grid, block and dynamic LDS, and for the search
+// kernels every scalar of MaxpathParams (a pointer as set / null; t_xs as the caller's or the workspace's).
+// tools/maxpath_launches.py reads it.  One integer test per launch when off.
+// --------------------------------------------------------------------------
+template <typename T> static const char *type_name() {
+    return std::is_same<T, float>::value ? "float" : std::is_same<T, double>::value ? "double"
+         : std::is_same<T, int32_t>::value ? "int32" : std::is_same<T, int64_t>::value ? "int64"
+         : std::is_same<T, uint8_t>::value ? "uint8" : std::is_same<T, uint16_t>::value ? "uint16" : "?";
+}
+static const char *const VT_NAME[3] = {"VT_F32", "VT_BF16", "VT_F16"};
+
+static void log_launch(dim3 grid, dim3 block, size_t lds, const MaxpathParams *p, const char *kernel_fmt, ...)
+    __attribute__((format(printf, 5, 6)));
+static void log_launch(dim3 grid, dim3 block, size_t lds, const MaxpathParams *p, const char *kernel_fmt, ...) {
+    char name[96];
+    va_list ap;
+    va_start(ap, kernel_fmt);
+    vsnprintf(name, sizeof(name), kernel_fmt, ap);
+    va_end(ap);
+    fprintf(stderr, "maxpath launch: %s grid=%u,%u,%u block=%u lds=%zu", name, grid.x, grid.y, grid.z, block.x, lds);
+    if (p) {
+        const bool ws_lengths = p->t_xs == reinterpret_cast<const int *>(reinterpret_cast<const unsigned char *>(p->status) + WS_HDR_BYTES);
+#define ALIGNER_SET(f) (p->f ? "set" : "null")
+        fprintf(stderr, " | B=%d Tx=%d Ty=%d ldv=%d NT=%d ROWS=%d WT=%d bits_in_lds=%d lds_bits_off=%d lds_prev_off=%d split_walk=%d"
+                        " lds_total=%d force_exact=%d neg=%g flags=0x%x verify=%d redo=%d path1_es=%d path1_one=0x%llx zero_blocks=%d"
+                        " zero_nt=%d zero_n16=%llu | value=%s mask=%s t_xs=%s t_ys=%s starts=%s tok=%s dur=%s bits=%s status=%s"
+                        " mflag=%s qout=%s xring=%s xflag=%s xwalk=%s stamps=%s dump=%s path1=%s zsync=%s",
+                p->B, p->Tx, p->Ty, p->ldv, p->NT, p->ROWS, p->WT, p->bits_in_lds, p->lds_bits_off, p->lds_prev_off, p->split_walk,
+                p->lds_total, p->force_exact, (double)p->neg, (unsigned)p->flags, p->verify, p->redo, p->path1_es, p->path1_one,
+                p->zero_blocks, p->zero_nt, p->zero_n16, ALIGNER_SET(value), ALIGNER_SET(mask),
+                !p->t_xs ? "null" : ws_lengths ? "workspace" : "caller", ALIGNER_SET(t_ys), ALIGNER_SET(starts), ALIGNER_SET(tok),
+                ALIGNER_SET(dur), ALIGNER_SET(bits), ALIGNER_SET(status), ALIGNER_SET(mflag), ALIGNER_SET(qout), ALIGNER_SET(xring),
+                ALIGNER_SET(xflag), ALIGNER_SET(xwalk), ALIGNER_SET(stamps), ALIGNER_SET(dump), ALIGNER_SET(path1), ALIGNER_SET(zsync));
+#undef ALIGNER_SET
     }
-    if (vec) return launch_pipelined_mm<NW, DEPTH, true, VT_F32>(p, maskmode, grid, block, lds, s);
-    return launch_pipelined_mm<NW, DEPTH, false, VT_F32>(p, maskmode, grid, block, lds, s);
+    fputc('\n', stderr);
 }
 
 __global__ __launch_bounds__(256) void xring_fill_kernel(uint4 *dst, int n16) {
@@ -1759,43 +1779,284 @@ __global__ __launch_bounds__(256) void xring_fill_kernel(uint4 *dst, int n16) {
     if (i < n16) dst[i] = make_uint4(XRING_EMPTY, XRING_EMPTY, XRING_EMPTY, XRING_EMPTY);
 }
 
-// two workgroups per utterance (grid 2B), 16-byte loaders only
-template <int VT>
-static int launch_pair_mm(MaxpathParams p, int maskmode, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    if (maskmode == 0) return launch_with_lds(maxpath_pipelined_kernel<4, 2, true, 0, VT, true>, grid, block, lds, s, p);
-    return launch_with_lds(maxpath_pipelined_kernel<4, 2, true, 1, VT, true>, grid, block, lds, s, p);
+// --------------------------------------------------------------------------
+// The plan of one search: which kernel, with how much LDS, how many zero workgroups and what in front of it.  Decided
+// once, from numbers alone (plan_search calls nothing of HIP), so that forward_impl is: check, plan, side launches, launch.
+// --------------------------------------------------------------------------
+enum SearchForm { FORM_PAIR, FORM_PIPELINED, FORM_GENERIC };
+enum MaskPlan {
+    MASK_NONE,            // no strict mask
+    MASK_MULTIPLY,        // value * mask in the loaders (MASKMODE 1)
+    MASK_VERIFY_FIRST,    // mask_verify_kernel in front; the pipelined kernel then decides per utterance (MASKMODE 2)
+    MASK_OPTIMISTIC       // the zero workgroups verify beside an unmasked search; a second launch redoes what they flag
+};
+
+struct SearchInputs {
+    int B, Tx, Ty, ldv, vt;
+    int flags;                      // the caller's (ALIGNER_F_WRITE_Q implies ALIGNER_F_FORCE_GENERIC: added by the plan)
+    bool lengths_given;
+    int path_es;                    // element size of the dense path asked for (0: none)
+    bool path_prezeroed;            // ... the caller's zeros (ALIGNER_F_PATH_PREZEROED): the search writes the ones only
+    bool value_al16, mask_al16, path_al16;      // 16-byte alignment of the three pointers
+    int cus;
+    size_t lds_max;
+};
+
+struct SearchPlan {
+    int form;                       // SearchForm
+    int NW, DEPTH, R;               // template arguments: (NW, DEPTH) of the pipelined and pair forms, R of the generic one
+    bool vec;
+    int maskmode, vt;
+    size_t lds;
+    int WT, bits_in_lds, lds_bits_off, lds_prev_off, split_walk;       // as in MaxpathParams
+    int zero_blocks, zero_nt;
+    unsigned long long zero_n16;
+    bool path_in_launch;            // the search launch finishes the dense path (no expand launch behind it)
+    int mask;                       // MaskPlan
+    bool derive_lengths;            // t_xs / t_ys come from the mask (mask_verify_kernel's piece 0, or lengths_kernel)
+    int flags;                      // MaxpathParams::flags
+    unsigned grid, block;
+};
+
+// The in-launch dense path: the first workgroups of a pipelined launch write the path's zeros on the CUs that the
+// `searching` workgroups leave idle (at least 32 of them), in 16-byte pieces.
+static bool zeros_fit_in_launch(const SearchInputs &in, int searching) {
+    return in.path_es > 0 && !in.path_prezeroed && !(in.flags & ALIGNER_F_SEPARATE_EXPAND) && in.cus - searching >= 32 &&
+           in.path_al16 && ((size_t)in.B * in.Tx * in.Ty * in.path_es) % 16 == 0;
 }
-static int launch_pair(MaxpathParams p, int maskmode, int vt, size_t lds, hipStream_t s) {
-    dim3 grid(2 * p.B + p.zero_blocks), block(4 * 128);
-    if (vt == VT_BF16) return launch_pair_mm<VT_BF16>(p, maskmode, grid, block, lds, s);
-    if (vt == VT_F16) return launch_pair_mm<VT_F16>(p, maskmode, grid, block, lds, s);
-    return launch_pair_mm<VT_F32>(p, maskmode, grid, block, lds, s);
+static void plan_zeros(SearchPlan &pl, const SearchInputs &in, int zero_blocks) {
+    pl.zero_blocks = zero_blocks;
+    pl.zero_nt = (in.flags & ALIGNER_F_STREAM_PATH) ? 1 : 0;
+    pl.zero_n16 = (size_t)in.B * in.Tx * in.Ty * in.path_es / 16;
+    pl.path_in_launch = true;
 }
 
-template <int R, int VT>
-static int launch_generic_vt(MaxpathParams p, int maskmode, size_t lds, hipStream_t s) {
-    dim3 grid(p.B), block(256);
-    if (maskmode == 0) return launch_with_lds(maxpath_generic_kernel<R, 0, VT>, grid, block, lds, s, p);
-    return launch_with_lds(maxpath_generic_kernel<R, 1, VT>, grid, block, lds, s, p);
+// Tiles in flight per loader wave of the one-workgroup form.  Eight waves (128 registers a lane) with the mask stream: one
+// (with two the loaders' 2 x 2 x 16 registers spilled: 30-41 VGPRs, 104-116 bytes of scratch a lane)
+constexpr int pipelined_depth(int NW, int maskmode) { return NW <= 2 ? 4 : (NW == 8 && maskmode) ? 1 : 2; }
+
+static int plan_search(const SearchInputs &in, const WsLayout &L, SearchPlan &pl) {
+    const int B = in.B, Tx = in.Tx, Ty = in.Ty, ldv = in.ldv, vt = in.vt, cus = in.cus;
+    const size_t lds_max = in.lds_max;
+    // ALIGNER_F_WRITE_Q: the pipelined kernel never materialises Q
+    const int flags = in.flags | ((in.flags & ALIGNER_F_WRITE_Q) ? ALIGNER_F_FORCE_GENERIC : 0);
+    const bool strict = (flags & ALIGNER_F_STRICT_MASK) != 0;
+    const int nw_need = (Tx + RPW - 1) / RPW;
+    pl = SearchPlan();
+    pl.vt = vt;
+    pl.flags = flags;
+    pl.derive_lengths = !in.lengths_given;
+    pl.path_in_launch = in.path_prezeroed;
+
+    // Strict mask on the kernels that can decide per utterance (the pipelined forms): one pass over the mask's
+    // rectangle verifies that the multiply is the identity there (and derives the lengths on the way), and the search
+    // then skips the mask stream (MASKMODE 2)
+    // (up to four waves of text rows: the eight-wave workgroup has 128 registers a lane and its strict form keeps one
+    // tile in flight instead of two to stay inside them; the two-workgroup form keeps the plain multiply)
+    bool dyn_mask = strict && !(flags & (ALIGNER_F_FORCE_GENERIC | ALIGNER_F_WRITE_Q)) && nw_need <= 4 &&
+                    !g_opt_maxpath_no_mask_verify;
+    // ... and where the search launch has zero workgroups (it writes the dense path on the CUs the batch leaves idle),
+    // THEY verify the mask, beside an optimistic search, and a second launch redoes the utterances they flag: no pass
+    // over the mask in front of the search at all
+    const bool opt_mask = dyn_mask && zeros_fit_in_launch(in, B) && (vt == VT_F32 || (Ty % 8 == 0 && in.value_al16)) &&
+                          !g_opt_maxpath_no_optimistic_mask;
+    if (opt_mask) dyn_mask = false;
+    // (decided before the form: a search that ends on the generic kernel after all multiplies, behind whichever of the two
+    // passes derived its lengths)
+    pl.mask = !strict ? MASK_NONE : dyn_mask ? MASK_VERIFY_FIRST : MASK_MULTIPLY;
+    const int maskmode = strict ? 1 : 0;
+    const int pipemask = dyn_mask ? 2 : opt_mask ? 0 : maskmode;        // the pipelined launches: decided per utterance on the device
+    // vec: 16-byte loads; the pipelined kernel's loaders address an utterance with 32-bit byte offsets
+    const int per16 = vt == VT_F32 ? 4 : 8;                      // scores per 16-byte load
+    const bool vec = (Ty % per16 == 0) && (ldv % per16 == 0) && in.value_al16 && (!maskmode || in.mask_al16) &&
+                     (size_t)Tx * (size_t)ldv * 4 < (1ull << 31);
+
+    // Long text (5..8 waves of rows) on a batch that leaves CUs idle: two workgroups per utterance, each the
+    // four-wave form with one compute wave per SIMD (maxpath_pipelined_kernel<.., PAIR>).  A full machine gains
+    // nothing from the split, and the second half runs some twenty phases behind the first (read-ahead, skew,
+    // forwarding, the boundary row's trip through memory).  Measured on full-length batches (in-kernel, two
+    // workgroups / one): [8,500,4000] 106 / 134 us, [8,500,2048] 68 / 76, [8,500,1536] 59 / 63, [8,500,1024] 50 / 50,
+    // [8,300,1536] 49 / 48; [16,400,2000] 65 / 75, [32,400,2000] 68 / 75, [64,400,2000] 74 / 76, [64,500,2048] 79 / 79:
+    // taken from 56 tiles on, for batches of at most an eighth of the CU count.
+    if (!(flags & (ALIGNER_F_FORCE_GENERIC | ALIGNER_F_ONE_CU)) && nw_need > 4 && nw_need <= 8 && vec && ldv == Ty &&
+        2 * B <= cus &&      // both halves of every utterance resident at once (see the kernel)
+        ((flags & ALIGNER_F_TWO_CUS) || (8 * B <= cus && L.NT >= 56))) {
+        const size_t fwd = align_up(((size_t)4 * (2 * 64 * TILE_LD + RING_T * RING_LD) + RING_T * RING_LD) * 4 + 16, 16);
+        const int WT = pick_window(L.NT, L.ROWS, Tx, lds_max);
+        if (WT > 0 && fwd <= lds_max && starts_bytes(Tx) <= fwd) {
+            // 16-byte loaders only, and no MASKMODE 2: more than four waves of rows keep the plain multiply (dyn_mask above)
+            pl.form = FORM_PAIR; pl.NW = 4; pl.DEPTH = 2; pl.vec = true; pl.maskmode = maskmode;
+            pl.WT = WT;
+            pl.lds = walk_bytes(WT, L.ROWS, Tx);
+            if (pl.lds < fwd) pl.lds = fwd;
+            // each half walks its own rows when all its decision words (NT tiles x 256 rows) fit in LDS beside the token
+            // starts (see the kernel); "maxpath_no_split_walk" keeps the one-walker form for A/B runs
+            const size_t split_lds = starts_bytes(Tx) + (size_t)L.NT * row_pitch(256) * 4;
+            if (split_lds <= lds_max && !g_opt_maxpath_no_split_walk) {
+                pl.split_walk = 1;
+                if (pl.lds < split_lds) pl.lds = split_lds;
+            }
+            // the dense path inside this launch (see the kernel): zero workgroups on the CUs the 2B halves leave idle
+            if (zeros_fit_in_launch(in, 2 * B)) {
+                // 48 zero workgroups, not one per idle CU: the zeros are not needed before the outputs (~90 us into the
+                // launch), and 240 workgroups flooding the write path for the first 13 us kept the 16 searching
+                // workgroups from priming their loaders.  [8,500,4000] bf16, int32 path, HIP events: 117.3 us with
+                // all idle CUs, 113.6 us with any count from 16 to 128 (durations only: 110.0 us)
+                int zb = cus - 2 * B < 48 ? cus - 2 * B : 48;
+                if (g_opt_maxpath_zero_blocks > 0 && g_opt_maxpath_zero_blocks <= cus - 2 * B) zb = g_opt_maxpath_zero_blocks;
+                plan_zeros(pl, in, zb);
+            }
+            pl.grid = 2 * B + pl.zero_blocks; pl.block = 4 * 128;
+            return ALIGNER_OK;
+        }
+    }
+    // One workgroup per utterance, a compute wave per 63 text rows.  16-bit scores are built on four or eight waves only
+    // (narrow text runs on NW = 4 with idle waves) and with 16-byte loaders only: everything else goes to the generic kernel
+    if (!(flags & ALIGNER_F_FORCE_GENERIC) && nw_need <= 8 && (vt == VT_F32 || vec)) {
+        const int NW = (nw_need <= 4 && vt != VT_F32) ? 4 : nw_need <= 1 ? 1 : nw_need <= 2 ? 2 : nw_need <= 4 ? 4 : 8;
+        const size_t fwd = align_up((size_t)NW * (2 * 64 * TILE_LD + RING_T * RING_LD) * 4 + 16, 16);
+        if (fwd <= lds_max && starts_bytes(Tx) <= fwd) {
+            const size_t bits_lds = (size_t)L.NT * row_pitch(L.ROWS) * 4;
+            if (L.NT <= 64 && fwd + bits_lds <= lds_max) {
+                pl.bits_in_lds = 1;
+                pl.lds_bits_off = (int)fwd;
+                pl.WT = L.NT;
+                pl.lds = fwd + bits_lds;
+                // room for the P table as well (and a walk with (W, P) in 128 + 64 VGPRs: NW <= 4): the
+                // backtrack's steps then cannot fail (walk_chunk_prev)
+                const size_t prev_lds = bits_lds + (size_t)row_pitch(L.ROWS) * 4;     // NT + 1 slots: tile t's entry in slot t + 1
+                if (NW <= 4 && L.NT < 64 && pl.lds + prev_lds <= lds_max && !(flags & ALIGNER_F_NO_PREV_TABLE)) {
+                    pl.lds_prev_off = (int)pl.lds;
+                    pl.lds += prev_lds;
+                }
+            } else {
+                pl.WT = pick_window(L.NT, L.ROWS, Tx, lds_max);
+                if (pl.WT > 0) {
+                    pl.lds = walk_bytes(pl.WT, L.ROWS, Tx);
+                    if (pl.lds < fwd) pl.lds = fwd;
+                }
+            }
+            if (pl.lds) {
+                pl.form = FORM_PIPELINED; pl.NW = NW; pl.vec = vec;
+                pl.maskmode = (NW == 8 && pipemask) ? 1 : pipemask;       // eight waves: the plain multiply only (dyn_mask above)
+                pl.DEPTH = pipelined_depth(NW, pl.maskmode);
+                // the dense path inside this launch: zero workgroups on the CUs the batch leaves idle (see the kernel)
+                if (zeros_fit_in_launch(in, B)) {
+                    // As many zero workgroups as write the zeros in about half the search's time (a CU streams ~50 GB/s, a
+                    // frame of the search takes ~31 ns: bytes / (775 * Ty)), not one per idle CU: the zeros are not needed
+                    // before the outputs, and the CUs they leave alone are other batches' (bench.py, fused form, three batches
+                    // in flight: 36.8-37.7 us a step with all 192, 33.7 with 64 or 128; ONE batch at a time: 55.7 -> 53.7 us;
+                    // 32 are too few: 61 us).  With the mask to verify they all come: the pieces are their work too.
+                    int zb = cus - B;
+                    if (!opt_mask) {
+                        const size_t pbytes = (size_t)B * Tx * Ty * in.path_es;
+                        const long long need = (long long)(pbytes / ((size_t)775 * (size_t)Ty)) + 1;
+                        const int zc = need < 48 ? 48 : (int)(need > cus - B ? cus - B : need);
+                        if (zc < zb) zb = zc;
+                    }
+                    if (g_opt_maxpath_zero_blocks >= 32 && g_opt_maxpath_zero_blocks <= cus - B) zb = g_opt_maxpath_zero_blocks;
+                    plan_zeros(pl, in, zb);
+                }
+                if (opt_mask) pl.mask = MASK_OPTIMISTIC;        // (opt_mask holds zeros_fit_in_launch(in, B): its zero workgroups exist)
+                pl.grid = B + pl.zero_blocks; pl.block = NW * 128;
+                return ALIGNER_OK;
+            }
+            pl.WT = 0;
+        }
+    }
+    // generic path
+    const int R = (Tx + 255) / 256;
+    if (R > 8) return fail(ALIGNER_EDOM, "Tx=%d exceeds the 2048 text rows the kernels support", Tx);
+    pl.form = FORM_GENERIC; pl.R = R <= 1 ? 1 : R <= 2 ? 2 : R <= 4 ? 4 : 8; pl.maskmode = maskmode;
+    const size_t fwd = (size_t)2 * (256 * pl.R + 1) * 4;
+    pl.WT = pick_window(L.NT, L.ROWS, Tx, lds_max);
+    if (pl.WT <= 0) return fail(ALIGNER_EDOM, "Tx=%d/Ty=%d too large for the backtrack window", Tx, Ty);
+    pl.lds = walk_bytes(pl.WT, L.ROWS, Tx);
+    if (pl.lds < fwd) pl.lds = fwd;
+    pl.grid = B; pl.block = 256;
+    return ALIGNER_OK;
 }
 
-template <int R>
-static int launch_generic(MaxpathParams p, int maskmode, int vt, size_t lds, hipStream_t s) {
-    if (vt == VT_BF16) return launch_generic_vt<R, VT_BF16>(p, maskmode, lds, s);
-    if (vt == VT_F16) return launch_generic_vt<R, VT_F16>(p, maskmode, lds, s);
-    return launch_generic_vt<R, VT_F32>(p, maskmode, lds, s);
+// --------------------------------------------------------------------------
+// The kernels that are built, one table per form; search_kernel() maps a plan to its entry.  An empty entry is a form
+// that plan_search routes around: 16-bit scores on one or two waves or with 4-byte loaders, eight waves with MASKMODE 2,
+// the pair and the generic form with MASKMODE 2.
+// --------------------------------------------------------------------------
+typedef void (*SearchKernel)(MaxpathParams);
+
+#define PIPE(NW, VEC, MM, VT) maxpath_pipelined_kernel<NW, pipelined_depth(NW, MM), VEC, MM, VT>
+#define PIPE_MM012(NW, VEC, VT) {PIPE(NW, VEC, 0, VT), PIPE(NW, VEC, 1, VT), PIPE(NW, VEC, 2, VT)}
+#define PIPE_MM01(NW, VEC, VT) {PIPE(NW, VEC, 0, VT), PIPE(NW, VEC, 1, VT)}
+#define PAIR_MM01(VT) {maxpath_pipelined_kernel<4, 2, true, 0, VT, true>, maxpath_pipelined_kernel<4, 2, true, 1, VT, true>}
+#define GENERIC_MM01(R, VT) {maxpath_generic_kernel<R, 0, VT>, maxpath_generic_kernel<R, 1, VT>}
+#define GENERIC_VT(R) {GENERIC_MM01(R, VT_F32), GENERIC_MM01(R, VT_BF16), GENERIC_MM01(R, VT_F16)}
+static const SearchKernel PIPELINED_KERNELS[4][3][2][3] = {      // [1, 2, 4, 8 waves][vt][vec][maskmode]
+    {{PIPE_MM012(1, false, VT_F32), PIPE_MM012(1, true, VT_F32)}},
+    {{PIPE_MM012(2, false, VT_F32), PIPE_MM012(2, true, VT_F32)}},
+    {{PIPE_MM012(4, false, VT_F32), PIPE_MM012(4, true, VT_F32)}, {{}, PIPE_MM012(4, true, VT_BF16)}, {{}, PIPE_MM012(4, true, VT_F16)}},
+    {{PIPE_MM01(8, false, VT_F32), PIPE_MM01(8, true, VT_F32)}, {{}, PIPE_MM01(8, true, VT_BF16)}, {{}, PIPE_MM01(8, true, VT_F16)}}};
+static const SearchKernel PAIR_KERNELS[3][3] = {PAIR_MM01(VT_F32), PAIR_MM01(VT_BF16), PAIR_MM01(VT_F16)};       // [vt][maskmode]
+static const SearchKernel GENERIC_KERNELS[4][3][3] = {GENERIC_VT(1), GENERIC_VT(2), GENERIC_VT(4), GENERIC_VT(8)};   // [R = 1, 2, 4, 8][vt][maskmode]
+#undef PIPE
+#undef PIPE_MM012
+#undef PIPE_MM01
+#undef PAIR_MM01
+#undef GENERIC_MM01
+#undef GENERIC_VT
+
+static SearchKernel search_kernel(const SearchPlan &pl) {       // (vt, vec, maskmode: 0..2, 0..1, 0..2 by construction)
+    const int n = pl.form == FORM_GENERIC ? pl.R : pl.NW, tier = n == 1 ? 0 : n == 2 ? 1 : n == 4 ? 2 : 3;
+    if (pl.form == FORM_GENERIC) return GENERIC_KERNELS[tier][pl.vt][pl.maskmode];
+    if (pl.form == FORM_PAIR) return PAIR_KERNELS[pl.vt][pl.maskmode];
+    return PIPELINED_KERNELS[tier][pl.vt][pl.vec][pl.maskmode];
+}
+
+static int launch_with_lds(const SearchPlan &pl, hipStream_t s, MaxpathParams p) {
+    const SearchKernel kernel = search_kernel(pl);
+    if (!kernel) return fail(ALIGNER_EINVAL, "internal: the plan names a search kernel that is not built");
+    const dim3 grid(pl.grid), block(pl.block);
+    p.lds_total = (int)pl.lds;
+    if (g_opt_maxpath_log_launch) {
+        if (pl.form == FORM_GENERIC)
+            log_launch(grid, block, pl.lds, &p, "maxpath_generic_kernel<%d,%d,%s>", pl.R, pl.maskmode, VT_NAME[pl.vt]);
+        else
+            log_launch(grid, block, pl.lds, &p, "maxpath_pipelined_kernel<%d,%d,%d,%d,%s,%d>", pl.NW, pl.DEPTH, (int)pl.vec,
+                       pl.maskmode, VT_NAME[pl.vt], pl.form == FORM_PAIR);
+    }
+    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), pl.lds));
+    hipLaunchKernelGGL(kernel, grid, block, pl.lds, s, p);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+
+// the side launches of a search: lengths from the mask, the mask's verification, the pair form's ring fill
+template <typename T, int VT = VT_F32>
+static int launch_lengths(const void *mask, int B, int Tx, int Ty, int32_t *t_xs, int32_t *t_ys, hipStream_t s) {
+    if (g_opt_maxpath_log_launch) log_launch(dim3(B), dim3(256), 0, nullptr, "lengths_kernel<%s,%s>", type_name<T>(), VT_NAME[VT]);
+    hipLaunchKernelGGL((lengths_kernel<T, VT>), dim3(B), dim3(256), 0, s, static_cast<const T *>(mask), Tx, Ty, t_xs, t_ys);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+
+template <int ES, int VT>
+static int launch_mask_verify(const void *mask, int B, int Tx, int Ty, const int *t_xs, const int *t_ys, int *lx, int *ly,
+                              int *mflag, unsigned one_bits, hipStream_t s) {
+    const dim3 grid(MV_CHUNKS, B), block(256);
+    if (g_opt_maxpath_log_launch) log_launch(grid, block, 0, nullptr, "mask_verify_kernel<%d,%s>", ES, VT_NAME[VT]);
+    hipLaunchKernelGGL((mask_verify_kernel<ES, VT>), grid, block, 0, s, mask, Tx, Ty, t_xs, t_ys, lx, ly, mflag, one_bits);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
 }
 
 static void set_path_ones(MaxpathParams &p, void *path, int path_dtype) {
     p.path1 = path;
     p.path1_es = dtype_size(path_dtype);
-    switch (path_dtype) {
-        case ALIGNER_DT_F32: p.path1_one = 0x3F800000ull; break;
-        case ALIGNER_DT_F64: p.path1_one = 0x3FF0000000000000ull; break;
-        case ALIGNER_DT_F16: p.path1_one = 0x3C00ull; break;
-        case ALIGNER_DT_BF16: p.path1_one = 0x3F80ull; break;
-        default: p.path1_one = 1ull; break;
-    }
+    p.path1_one = 1ull;
+    (void)with_path_one(path_dtype, [&](auto one) {
+        p.path1_one = 0;
+        memcpy(&p.path1_one, &one, sizeof(one));       // (little endian: the low bytes)
+        return ALIGNER_OK;
+    });
 }
 
 static int forward_impl(const void *value, int value_dtype, const void *mask, int mask_dtype, const int32_t *t_xs,
@@ -1807,9 +2068,10 @@ static int forward_impl(const void *value, int value_dtype, const void *mask, in
     // ALIGNER_F_PATH_PREZEROED), its zeros too where the pipelined kernel runs with zero workgroups; *path_done says
     // whether it did (otherwise the caller launches expand)
     if (path_done) *path_done = false;
-    void *path_prezeroed = path_is_zero ? path_out : nullptr;
+
+    // 1. the arguments
     if (!value || !ws) return fail(ALIGNER_EINVAL, "value/workspace pointer is null");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (int rc = check_shape(B, Tx, Ty)) return rc;
     if ((size_t)Tx * (size_t)Ty >= (1ull << 31))
         return fail(ALIGNER_EDOM, "Tx*Ty=%zu exceeds 2^31", (size_t)Tx * Ty);
     if ((!t_xs || !t_ys) && !mask)
@@ -1832,47 +2094,47 @@ static int forward_impl(const void *value, int value_dtype, const void *mask, in
     if (B == 0) return ALIGNER_OK;
     const WsLayout L = ws_layout(B, Tx, Ty);
     if (ws_bytes < L.total) return fail(ALIGNER_ENOSPC, "workspace %zu < %zu bytes", ws_bytes, L.total);
-    unsigned char *wsb = static_cast<unsigned char *>(ws);
+    if ((flags & ALIGNER_F_WRITE_Q) && (vt != VT_F32 || (flags & ALIGNER_F_STRICT_MASK)))
+        return fail(ALIGNER_EINVAL, "ALIGNER_F_WRITE_Q takes fp32 scores without a strict mask (maximum_path_c's contract)");
 
-    // Strict mask on the kernels that can decide per utterance (the pipelined forms): one pass over the mask's
-    // rectangle verifies that the multiply is the identity there (and derives the lengths on the way), and the search
-    // then skips the mask stream (MASKMODE 2)
-    // (up to four waves of text rows: the eight-wave workgroup has 128 registers a lane and its strict form keeps one
-    // tile in flight instead of two to stay inside them; the two-workgroup form keeps the plain multiply)
-    bool dyn_mask = (flags & ALIGNER_F_STRICT_MASK) && !(flags & (ALIGNER_F_FORCE_GENERIC | ALIGNER_F_WRITE_Q)) &&
-                    (Tx + RPW - 1) / RPW <= 4 && !g_opt_maxpath_no_mask_verify;
-    // ... and where the search launch has zero workgroups (it writes the dense path on the CUs the batch leaves idle),
-    // THEY verify the mask, beside an optimistic search, and a second launch redoes the utterances they flag: no pass
-    // over the mask in front of the search at all
-    const bool opt_mask = dyn_mask && path_out && !path_is_zero && !(flags & ALIGNER_F_SEPARATE_EXPAND) &&
-                          device_cu_count() - B >= 32 && (reinterpret_cast<uintptr_t>(path_out) & 15) == 0 &&
-                          ((size_t)B * Tx * Ty * dtype_size(path_dtype)) % 16 == 0 && dtype_size(path_dtype) > 0 &&
-                          (vt == VT_F32 || (Ty % 8 == 0 && (reinterpret_cast<uintptr_t>(value) & 15) == 0)) &&
-                          !g_opt_maxpath_no_optimistic_mask;
-    if (opt_mask) dyn_mask = false;
-    if (dyn_mask) {
-        int *lx = reinterpret_cast<int *>(wsb + L.len_off), *ly = lx + B;
-        int *mf = reinterpret_cast<int *>(wsb + L.mflag_off);
-        const bool derive = !t_xs || !t_ys;
-        dim3 grid(MV_CHUNKS, B), block(256);
-        if (vt == VT_F32)
-            hipLaunchKernelGGL((mask_verify_kernel<4, VT_F32>), grid, block, 0, s, mask, Tx, Ty, derive ? nullptr : t_xs,
-                               derive ? nullptr : t_ys, lx, ly, mf, 0x3F800000u);
-        else if (vt == VT_BF16)
-            hipLaunchKernelGGL((mask_verify_kernel<2, VT_BF16>), grid, block, 0, s, mask, Tx, Ty, derive ? nullptr : t_xs,
-                               derive ? nullptr : t_ys, lx, ly, mf, 0x3F80u);
-        else
-            hipLaunchKernelGGL((mask_verify_kernel<2, VT_F16>), grid, block, 0, s, mask, Tx, Ty, derive ? nullptr : t_xs,
-                               derive ? nullptr : t_ys, lx, ly, mf, 0x3C00u);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-        if (derive) { t_xs = lx; t_ys = ly; }
-    } else if (!t_xs || !t_ys) {
-        int *lx = reinterpret_cast<int *>(wsb + L.len_off), *ly = lx + B;
-        int rc = aligner_lengths_from_mask(mask, mask_dtype, B, Tx, Ty, lx, ly, s);
+    // 2. the plan
+    const auto al16 = [](const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
+    SearchInputs in;
+    in.B = B; in.Tx = Tx; in.Ty = Ty; in.ldv = ldv; in.vt = vt; in.flags = flags;
+    in.lengths_given = t_xs && t_ys;
+    in.path_es = path_out ? dtype_size(path_dtype) : 0;
+    in.path_prezeroed = path_out && path_is_zero;
+    in.value_al16 = al16(value); in.mask_al16 = al16(mask); in.path_al16 = al16(path_out);
+    in.cus = device_cu_count();
+    in.lds_max = (size_t)device_lds_limit();
+    SearchPlan pl;
+    if (int rc = plan_search(in, L, pl)) return rc;
+
+    // 3. the side launches the plan names
+    unsigned char *wsb = static_cast<unsigned char *>(ws);
+    int *lx = reinterpret_cast<int *>(wsb + L.len_off), *ly = lx + B;
+    int *mflag = reinterpret_cast<int *>(wsb + L.mflag_off);
+    if (pl.mask == MASK_VERIFY_FIRST) {
+        const int *gx = pl.derive_lengths ? nullptr : t_xs, *gy = pl.derive_lengths ? nullptr : t_ys;
+        int rc = vt == VT_F32  ? launch_mask_verify<4, VT_F32>(mask, B, Tx, Ty, gx, gy, lx, ly, mflag, 0x3F800000u, s)
+               : vt == VT_BF16 ? launch_mask_verify<2, VT_BF16>(mask, B, Tx, Ty, gx, gy, lx, ly, mflag, 0x3F80u, s)
+                               : launch_mask_verify<2, VT_F16>(mask, B, Tx, Ty, gx, gy, lx, ly, mflag, 0x3C00u, s);
         if (rc) return rc;
-        t_xs = lx; t_ys = ly;
+    } else if (pl.derive_lengths) {
+        if (int rc = aligner_lengths_from_mask(mask, mask_dtype, B, Tx, Ty, lx, ly, s)) return rc;
+    }
+    if (pl.derive_lengths) { t_xs = lx; t_ys = ly; }
+    if (pl.form == FORM_PAIR) {
+        // the boundary ring and the done words start every launch as 0xFFFFFFFF (a kernel of our own: a captured
+        // hipMemsetAsync node did not refill the ring when the graph was replayed)
+        const int n16 = (int)(L.xring_bytes / 16);
+        if (g_opt_maxpath_log_launch) log_launch(dim3((n16 + 255) / 256), dim3(256), 0, nullptr, "xring_fill_kernel");
+        hipLaunchKernelGGL(xring_fill_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s,
+                           reinterpret_cast<uint4 *>(wsb + L.xring_off), n16);
+        ALIGNER_HIP_CHECK(hipGetLastError());
     }
 
+    // 4. the parameters, and the launch
     MaxpathParams p;
     p.value = value;
     p.mask = (flags & ALIGNER_F_STRICT_MASK) ? mask : nullptr;
@@ -1882,174 +2144,35 @@ static int forward_impl(const void *value, int value_dtype, const void *mask, in
     p.dur = dur_out;
     p.bits = reinterpret_cast<unsigned *>(wsb + L.bits_off);
     p.status = reinterpret_cast<int *>(wsb + L.status_off);
-    p.mflag = reinterpret_cast<int *>(wsb + L.mflag_off);
+    p.mflag = mflag;
     p.verify = 0; p.redo = 0; p.ldv = ldv;
     p.B = B; p.Tx = Tx; p.Ty = Ty; p.NT = L.NT; p.ROWS = L.ROWS;
-    p.neg = neg; p.flags = flags;
-    p.bits_in_lds = 0; p.lds_bits_off = 0; p.lds_prev_off = 0;
+    p.WT = pl.WT;
+    p.bits_in_lds = pl.bits_in_lds; p.lds_bits_off = pl.lds_bits_off; p.lds_prev_off = pl.lds_prev_off;
     p.force_exact = !(neg - neg == 0.0f);            // NaN / inf max_neg_val
-    p.stamps = g_debug_stamps;
-    p.dump = nullptr;
-    p.qout = nullptr;
-    p.path1 = nullptr; p.path1_es = 0; p.path1_one = 0;
-    if (path_prezeroed) set_path_ones(p, path_prezeroed, path_dtype);
-    p.zero_blocks = 0; p.zero_nt = 0; p.zero_n16 = 0;
-    p.zsync = reinterpret_cast<int *>(wsb + L.status_off + 16);
-    if (path_prezeroed && path_done) *path_done = true;
+    p.neg = neg; p.flags = pl.flags;
+    p.qout = (flags & ALIGNER_F_WRITE_Q) ? const_cast<float *>(static_cast<const float *>(value)) : nullptr;
+    p.lds_total = 0;                                 // (launch_with_lds)
     p.xring = reinterpret_cast<unsigned *>(wsb + L.xring_off);
     p.xflag = reinterpret_cast<int *>(wsb + L.xring_off + (size_t)B * L.NT * TC * sizeof(unsigned));
     p.xwalk = reinterpret_cast<unsigned *>(p.xflag + B);
-    p.split_walk = 0;
-    if (flags & ALIGNER_F_WRITE_Q) {
-        if (vt != VT_F32 || (flags & ALIGNER_F_STRICT_MASK))
-            return fail(ALIGNER_EINVAL, "ALIGNER_F_WRITE_Q takes fp32 scores without a strict mask (maximum_path_c's contract)");
-        p.qout = const_cast<float *>(static_cast<const float *>(value));
-        flags |= ALIGNER_F_FORCE_GENERIC;           // the pipelined kernel never materialises Q
-        p.flags = flags;
-    }
-    const int maskmode = (flags & ALIGNER_F_STRICT_MASK) ? 1 : 0;
-    const int pipemask = dyn_mask ? 2 : opt_mask ? 0 : maskmode;        // the pipelined launches: decided per utterance on the device
-    const size_t lds_max = (size_t)lds_limit();
-    // vec: 16-byte loads; the pipelined kernel's loaders address an utterance with 32-bit byte offsets
-    const int per16 = vt == VT_F32 ? 4 : 8;                      // scores per 16-byte load
-    const bool vec = (Ty % per16 == 0) && (ldv % per16 == 0) && ((reinterpret_cast<uintptr_t>(value) & 15) == 0) &&
-                     (!maskmode || (reinterpret_cast<uintptr_t>(mask) & 15) == 0) &&
-                     (size_t)Tx * (size_t)ldv * 4 < (1ull << 31);
-
-    const int nw_need = (Tx + RPW - 1) / RPW;
-    // Long text (5..8 waves of rows) on a batch that leaves CUs idle: two workgroups per utterance, each the
-    // four-wave form with one compute wave per SIMD (maxpath_pipelined_kernel<.., PAIR>).  A full machine gains
-    // nothing from the split, and the second half runs some twenty phases behind the first (read-ahead, skew,
-    // forwarding, the boundary row's trip through memory).  Measured on full-length batches (in-kernel, two
-    // workgroups / one): [8,500,4000] 106 / 134 us, [8,500,2048] 68 / 76, [8,500,1536] 59 / 63, [8,500,1024] 50 / 50,
-    // [8,300,1536] 49 / 48; [16,400,2000] 65 / 75, [32,400,2000] 68 / 75, [64,400,2000] 74 / 76, [64,500,2048] 79 / 79:
-    // taken from 56 tiles on, for batches of at most an eighth of the CU count.
-    if (!(flags & (ALIGNER_F_FORCE_GENERIC | ALIGNER_F_ONE_CU)) && nw_need > 4 && nw_need <= 8 && vec && ldv == Ty &&
-        2 * B <= device_cu_count() &&      // both halves of every utterance resident at once (see the kernel)
-        ((flags & ALIGNER_F_TWO_CUS) || (8 * B <= device_cu_count() && L.NT >= 56))) {
-        const size_t fwd = align_up(((size_t)4 * (2 * 64 * TILE_LD + RING_T * RING_LD) + RING_T * RING_LD) * 4 + 16, 16);
-        p.WT = pick_window(L.NT, L.ROWS, Tx, lds_max);
-        if (p.WT > 0 && fwd <= lds_max && starts_bytes(Tx) <= fwd) {
-            size_t lds = walk_bytes(p.WT, L.ROWS, Tx);
-            if (lds < fwd) lds = fwd;
-            // each half walks its own rows when all its decision words (NT tiles x 256 rows) fit in LDS beside the token
-            // starts (see the kernel); "maxpath_no_split_walk" keeps the one-walker form for A/B runs
-            const size_t split_lds = starts_bytes(Tx) + (size_t)L.NT * row_pitch(256) * 4;
-            if (split_lds <= lds_max && !g_opt_maxpath_no_split_walk) {
-                p.split_walk = 1;
-                if (lds < split_lds) lds = split_lds;
-            }
-            // the boundary ring and the done words start every launch as 0xFFFFFFFF (a kernel of our own: a captured
-            // hipMemsetAsync node did not refill the ring when the graph was replayed)
-            const int n16 = (int)(L.xring_bytes / 16);
-            hipLaunchKernelGGL(xring_fill_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s,
-                               reinterpret_cast<uint4 *>(wsb + L.xring_off), n16);
-            ALIGNER_HIP_CHECK(hipGetLastError());
-            {   // the dense path inside this launch (see the kernel): zero workgroups on the CUs the 2B halves leave idle
-                const int cus = device_cu_count();
-                const size_t pbytes = path_out ? (size_t)B * Tx * Ty * dtype_size(path_dtype) : 0;
-                if (path_out && !path_is_zero && !(flags & ALIGNER_F_SEPARATE_EXPAND) && cus - 2 * B >= 32 &&
-                    (reinterpret_cast<uintptr_t>(path_out) & 15) == 0 && pbytes % 16 == 0 && dtype_size(path_dtype) > 0) {
-                    // 48 zero workgroups, not one per idle CU: the zeros are not needed before the outputs (~90 us into the
-                    // launch), and 240 workgroups flooding the write path for the first 13 us kept the 16 searching
-                    // workgroups from priming their loaders.  [8,500,4000] bf16, int32 path, HIP events: 117.3 us with
-                    // all idle CUs, 113.6 us with any count from 16 to 128 (durations only: 110.0 us)
-                    p.zero_blocks = cus - 2 * B < 48 ? cus - 2 * B : 48;
-                    if (g_opt_maxpath_zero_blocks > 0 && g_opt_maxpath_zero_blocks <= cus - 2 * B) p.zero_blocks = g_opt_maxpath_zero_blocks;
-                    p.zero_nt = (flags & ALIGNER_F_STREAM_PATH) ? 1 : 0;
-                    p.zero_n16 = pbytes / 16;
-                    set_path_ones(p, path_out, path_dtype);
-                    if (path_done) *path_done = true;
-                }
-            }
-            return launch_pair(p, pipemask, vt, lds, s);
-        }
-    }
-    if (!(flags & ALIGNER_F_FORCE_GENERIC) && nw_need <= 8 && (vt == VT_F32 || vec)) {
-        const int NW = (nw_need <= 4 && vt != VT_F32) ? 4 : nw_need <= 1 ? 1 : nw_need <= 2 ? 2 : nw_need <= 4 ? 4 : 8;
-        const size_t fwd = align_up((size_t)NW * (2 * 64 * TILE_LD + RING_T * RING_LD) * 4 + 16, 16);
-        if (fwd <= lds_max && starts_bytes(Tx) <= fwd) {
-            size_t lds = 0;
-            const size_t bits_lds = (size_t)L.NT * row_pitch(L.ROWS) * 4;
-            if (L.NT <= 64 && fwd + bits_lds <= lds_max) {
-                p.bits_in_lds = 1;
-                p.lds_bits_off = (int)fwd;
-                p.WT = L.NT;
-                lds = fwd + bits_lds;
-                // room for the P table as well (and a walk with (W, P) in 128 + 64 VGPRs: NW <= 4): the
-                // backtrack's steps then cannot fail (walk_chunk_prev)
-                const size_t prev_lds = bits_lds + (size_t)row_pitch(L.ROWS) * 4;     // NT + 1 slots: tile t's entry in slot t + 1
-                if (NW <= 4 && L.NT < 64 && lds + prev_lds <= lds_max && !(flags & ALIGNER_F_NO_PREV_TABLE)) {
-                    p.lds_prev_off = (int)lds;
-                    lds += prev_lds;
-                }
-            } else {
-                p.WT = pick_window(L.NT, L.ROWS, Tx, lds_max);
-                if (p.WT > 0) {
-                    lds = walk_bytes(p.WT, L.ROWS, Tx);
-                    if (lds < fwd) lds = fwd;
-                }
-            }
-            if (lds) {
-                // the dense path inside this launch: zero workgroups on the CUs the batch leaves idle (see the kernel)
-                const int cus = device_cu_count();
-                const size_t pbytes = path_out ? (size_t)B * Tx * Ty * dtype_size(path_dtype) : 0;
-                if (path_out && !path_is_zero && !(flags & ALIGNER_F_SEPARATE_EXPAND) && cus - B >= 32 &&
-                    (reinterpret_cast<uintptr_t>(path_out) & 15) == 0 && pbytes % 16 == 0 && dtype_size(path_dtype) > 0) {
-                    // As many zero workgroups as write the zeros in about half the search's time (a CU streams ~50 GB/s, a
-                    // frame of the search takes ~31 ns: bytes / (775 * Ty)), not one per idle CU: the zeros are not needed
-                    // before the outputs, and the CUs they leave alone are other batches' (bench.py, fused form, three batches
-                    // in flight: 36.8-37.7 us a step with all 192, 33.7 with 64 or 128; ONE batch at a time: 55.7 -> 53.7 us;
-                    // 32 are too few: 61 us).  With the mask to verify they all come: the pieces are their work too.
-                    p.zero_blocks = cus - B;
-                    if (!opt_mask) {
-                        const long long need = (long long)(pbytes / ((size_t)775 * (size_t)Ty)) + 1;
-                        const int zc = need < 48 ? 48 : (int)(need > cus - B ? cus - B : need);
-                        if (zc < p.zero_blocks) p.zero_blocks = zc;
-                    }
-                    if (g_opt_maxpath_zero_blocks >= 32 && g_opt_maxpath_zero_blocks <= cus - B) p.zero_blocks = g_opt_maxpath_zero_blocks;
-                    p.zero_nt = (flags & ALIGNER_F_STREAM_PATH) ? 1 : 0;
-                    p.zero_n16 = pbytes / 16;
-                    set_path_ones(p, path_out, path_dtype);
-                    if (path_done) *path_done = true;
-                }
-                auto launch = [&](const MaxpathParams &q, int mm) {
-                    switch (NW) {
-                        case 1: return launch_pipelined<1, 4>(q, vec, mm, vt, lds, s);
-                        case 2: return launch_pipelined<2, 4>(q, vec, mm, vt, lds, s);
-                        case 4: return launch_pipelined<4, 2>(q, vec, mm, vt, lds, s);
-                        default: return launch_pipelined<8, 2>(q, vec, mm, vt, lds, s);
-                    }
-                };
-                if (opt_mask && p.zero_blocks > 0) {
-                    p.mask = mask;
-                    p.verify = 1;
-                    int rc = launch(p, 0);                         // optimistic search + zeros + verification
-                    if (rc != ALIGNER_OK) return rc;
-                    MaxpathParams r = p;                           // the redo of the flagged utterances: ones only, no zero workgroups
-                    r.verify = 0; r.redo = 1; r.zero_blocks = 0; r.zero_n16 = 0;
-                    return launch(r, 1);
-                }
-                return launch(p, opt_mask ? maskmode : pipemask);   // (no zero workgroups after all: the plain multiply)
-            }
-        }
-    }
-    // generic path
-    const int R = (Tx + 255) / 256;
-    if (R > 8) return fail(ALIGNER_EDOM, "Tx=%d exceeds the 2048 text rows the kernels support", Tx);
-    const int RR = R <= 1 ? 1 : R <= 2 ? 2 : R <= 4 ? 4 : 8;
-    const size_t fwd = (size_t)2 * (256 * RR + 1) * 4;
-    p.WT = pick_window(L.NT, L.ROWS, Tx, lds_max);
-    if (p.WT <= 0) return fail(ALIGNER_EDOM, "Tx=%d/Ty=%d too large for the backtrack window", Tx, Ty);
-    size_t lds = walk_bytes(p.WT, L.ROWS, Tx);
-    if (lds < fwd) lds = fwd;
-    switch (RR) {
-        case 1: return launch_generic<1>(p, maskmode, vt, lds, s);
-        case 2: return launch_generic<2>(p, maskmode, vt, lds, s);
-        case 4: return launch_generic<4>(p, maskmode, vt, lds, s);
-        default: return launch_generic<8>(p, maskmode, vt, lds, s);
-    }
+    p.split_walk = pl.split_walk;
+    p.stamps = g_debug_stamps;
+    p.dump = nullptr;
+    p.path1 = nullptr; p.path1_es = 0; p.path1_one = 0;
+    if (pl.path_in_launch) set_path_ones(p, path_out, path_dtype);
+    p.zero_blocks = pl.zero_blocks; p.zero_nt = pl.zero_nt; p.zero_n16 = pl.zero_n16;
+    p.zsync = reinterpret_cast<int *>(wsb + L.status_off + 16);
+    if (path_done) *path_done = pl.path_in_launch;
+    if (pl.mask != MASK_OPTIMISTIC) return launch_with_lds(pl, s, p);
+    p.verify = 1;
+    if (int rc = launch_with_lds(pl, s, p)) return rc;       // optimistic search + zeros + verification
+    SearchPlan redo = pl;                                    // the redo of the flagged utterances: ones only, no zero workgroups
+    redo.maskmode = 1; redo.grid = B;
+    p.verify = 0; p.redo = 1; p.zero_blocks = 0; p.zero_n16 = 0;
+    return launch_with_lds(redo, s, p);
 }
+
 
 template <typename T>
 static int launch_expand(const int *starts, void *path, int B, int Tx, int Ty, T one, bool stream_path, hipStream_t s) {
@@ -2065,6 +2188,8 @@ static int launch_expand(const int *starts, void *path, int B, int Tx, int Ty, T
     }
     dim3 grid((Ty + 1023) / 1024, (Tx + rpb - 1) / rpb, B), block(256);
     const bool vec = (Ty % 4 == 0) && ((reinterpret_cast<uintptr_t>(path) % (sizeof(T) * 4)) == 0);
+    if (g_opt_maxpath_log_launch)
+        log_launch(grid, block, 0, nullptr, "expand_kernel<%s,%d,%d> rows_per_block=%d", type_name<T>(), vec, vec && stream_path, rpb);
     if (vec && stream_path)
         hipLaunchKernelGGL((expand_kernel<T, true, true>), grid, block, 0, s, starts, static_cast<T *>(path), Tx, Ty, rpb, one);
     else if (vec)
@@ -2126,16 +2251,37 @@ static int launch_scatter(const int *starts, void *path, int B, int Tx, int Ty, 
 
 static int expand_impl(const int *starts, void *path, int path_dtype, int B, int Tx, int Ty, bool stream_path, hipStream_t s) {
     if (B > 65535 || (Tx + 7) / 8 > 65535) return fail(ALIGNER_EDOM, "grid too large");
-    switch (path_dtype) {
-        case ALIGNER_DT_F32: return launch_expand<float>(starts, path, B, Tx, Ty, 1.0f, stream_path, s);
-        case ALIGNER_DT_F64: return launch_expand<double>(starts, path, B, Tx, Ty, 1.0, stream_path, s);
-        case ALIGNER_DT_I32: return launch_expand<int32_t>(starts, path, B, Tx, Ty, 1, stream_path, s);
-        case ALIGNER_DT_I64: return launch_expand<int64_t>(starts, path, B, Tx, Ty, 1, stream_path, s);
-        case ALIGNER_DT_U8:  return launch_expand<uint8_t>(starts, path, B, Tx, Ty, 1, stream_path, s);
-        case ALIGNER_DT_F16: return launch_expand<uint16_t>(starts, path, B, Tx, Ty, 0x3C00, stream_path, s);
-        case ALIGNER_DT_BF16: return launch_expand<uint16_t>(starts, path, B, Tx, Ty, 0x3F80, stream_path, s);
-        default: return fail(ALIGNER_EINVAL, "path dtype %d not supported", path_dtype);
-    }
+    return with_path_one(path_dtype, [&](auto one) { return launch_expand(starts, path, B, Tx, Ty, one, stream_path, s); });
+}
+
+static const int *ws_starts(const void *ws, int B, int Tx, int Ty) {
+    return reinterpret_cast<const int *>(static_cast<const unsigned char *>(ws) + ws_layout(B, Tx, Ty).starts_off);
+}
+
+template <bool STREAM>
+static int launch_zero_path(unsigned blocks, unsigned char *dst, size_t n16, unsigned char *tail, int ntail, hipStream_t s) {
+    hipLaunchKernelGGL(zero_path_kernel<STREAM>, dim3(blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(dst), n16, tail, ntail);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+
+static int check_path_dtype(const void *path_out, int path_dtype) {
+    if (path_out && dtype_size(path_dtype) == 0) return fail(ALIGNER_EINVAL, "path dtype %d not supported", path_dtype);
+    return ALIGNER_OK;
+}
+
+// aligner_maxpath and aligner_maxpath_ld behind their own checks: the search, then the dense path where the search left it
+static int search_and_path(const void *value, int value_dtype, const void *mask, int mask_dtype, const int32_t *t_xs,
+                           const int32_t *t_ys, void *path_out, int path_dtype, int32_t *tok_out, int32_t *dur_out, void *ws,
+                           size_t ws_bytes, int B, int Tx, int Ty, float max_neg_val, int flags, void *stream, int ld_value) {
+    // ALIGNER_F_PATH_PREZEROED: the search kernel itself writes the ones into the caller's zeros -- no expand launch
+    // and without it the pipelined kernel's own zero workgroups do the whole path where they can (path_done)
+    const bool prez = path_out && (flags & ALIGNER_F_PATH_PREZEROED);
+    bool path_done = false;
+    int rc = forward_impl(value, value_dtype, mask, mask_dtype, t_xs, t_ys, tok_out, dur_out, ws, ws_bytes, B, Tx, Ty,
+                          max_neg_val, flags, static_cast<hipStream_t>(stream), path_out, path_dtype, prez, &path_done, ld_value);
+    if (rc || !path_out || B == 0 || path_done) return rc;
+    return aligner_maxpath_expand_ex(ws, path_out, path_dtype, B, Tx, Ty, flags, stream);
 }
 
 }  // namespace aligner
@@ -2152,35 +2298,17 @@ size_t aligner_maxpath_workspace_bytes(int B, int Tx, int Ty) {
 int aligner_lengths_from_mask(const void *mask, int mask_dtype, int B, int Tx, int Ty,
                               int32_t *t_xs, int32_t *t_ys, void *stream) {
     if (!mask || !t_xs || !t_ys) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (int rc = check_shape(B, Tx, Ty)) return rc;
     if (B == 0) return ALIGNER_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (mask_dtype) {
-        case ALIGNER_DT_F32:
-            hipLaunchKernelGGL(lengths_kernel<float>, dim3(B), dim3(256), 0, s,
-                               static_cast<const float *>(mask), Tx, Ty, t_xs, t_ys);
-            break;
-        case ALIGNER_DT_U8:
-            hipLaunchKernelGGL(lengths_kernel<unsigned char>, dim3(B), dim3(256), 0, s,
-                               static_cast<const unsigned char *>(mask), Tx, Ty, t_xs, t_ys);
-            break;
-        case ALIGNER_DT_I32:
-            hipLaunchKernelGGL(lengths_kernel<int>, dim3(B), dim3(256), 0, s,
-                               static_cast<const int *>(mask), Tx, Ty, t_xs, t_ys);
-            break;
-        case ALIGNER_DT_BF16:
-            hipLaunchKernelGGL((lengths_kernel<unsigned short, VT_BF16>), dim3(B), dim3(256), 0, s,
-                               static_cast<const unsigned short *>(mask), Tx, Ty, t_xs, t_ys);
-            break;
-        case ALIGNER_DT_F16:
-            hipLaunchKernelGGL((lengths_kernel<unsigned short, VT_F16>), dim3(B), dim3(256), 0, s,
-                               static_cast<const unsigned short *>(mask), Tx, Ty, t_xs, t_ys);
-            break;
-        default:
-            return fail(ALIGNER_EINVAL, "mask dtype %d not supported (use F32, BF16, F16, U8 or I32)", mask_dtype);
+        case ALIGNER_DT_F32: return launch_lengths<float>(mask, B, Tx, Ty, t_xs, t_ys, s);
+        case ALIGNER_DT_U8: return launch_lengths<unsigned char>(mask, B, Tx, Ty, t_xs, t_ys, s);
+        case ALIGNER_DT_I32: return launch_lengths<int>(mask, B, Tx, Ty, t_xs, t_ys, s);
+        case ALIGNER_DT_BF16: return launch_lengths<unsigned short, VT_BF16>(mask, B, Tx, Ty, t_xs, t_ys, s);
+        case ALIGNER_DT_F16: return launch_lengths<unsigned short, VT_F16>(mask, B, Tx, Ty, t_xs, t_ys, s);
+        default: return fail(ALIGNER_EINVAL, "mask dtype %d not supported (use F32, BF16, F16, U8 or I32)", mask_dtype);
     }
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    return ALIGNER_OK;
 }
 
 int aligner_maxpath_forward(const void *value, int value_dtype, const void *mask, int mask_dtype,
@@ -2202,17 +2330,15 @@ int aligner_maxpath_forward_f32(const float *value, const void *mask, int mask_d
 int aligner_maxpath_expand_ex(const void *ws, void *path, int path_dtype, int B, int Tx, int Ty, int flags,
                               void *stream) {
     if (!ws || !path) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (int rc = check_shape(B, Tx, Ty)) return rc;
     if (B == 0) return ALIGNER_OK;
-    const WsLayout L = ws_layout(B, Tx, Ty);
-    const int *starts = reinterpret_cast<const int *>(static_cast<const unsigned char *>(ws) + L.starts_off);
-    return expand_impl(starts, path, path_dtype, B, Tx, Ty, (flags & ALIGNER_F_STREAM_PATH) != 0,
+    return expand_impl(ws_starts(ws, B, Tx, Ty), path, path_dtype, B, Tx, Ty, (flags & ALIGNER_F_STREAM_PATH) != 0,
                        static_cast<hipStream_t>(stream));
 }
 
 int aligner_maxpath_zero_path(void *path, int path_dtype, int B, int Tx, int Ty, int flags, void *stream) {
     if (!path) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (int rc = check_shape(B, Tx, Ty)) return rc;
     const int es = dtype_size(path_dtype);
     if (es == 0) return fail(ALIGNER_EINVAL, "path dtype %d not supported", path_dtype);
     if (B == 0) return ALIGNER_OK;
@@ -2223,42 +2349,24 @@ int aligner_maxpath_zero_path(void *path, int path_dtype, int B, int Tx, int Ty,
     const size_t head = (16 - (reinterpret_cast<uintptr_t>(pb) & 15)) & 15;
     const size_t h = head < bytes ? head : bytes;
     const size_t n16 = (bytes - h) / 16, tail = (bytes - h) - n16 * 16;
-    if (h) {
-        hipLaunchKernelGGL(zero_path_kernel<false>, dim3(1), dim3(256), 0, s, reinterpret_cast<uint4 *>(pb), (size_t)0, pb, (int)h);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
+    if (h)
+        if (int rc = launch_zero_path<false>(1, pb, 0, pb, (int)h, s)) return rc;
     size_t blocks = (n16 + 255) / 256;
     const size_t cap = (size_t)device_cu_count() * 16;
     blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
-    if (flags & ALIGNER_F_STREAM_PATH)
-        hipLaunchKernelGGL(zero_path_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(pb + h), n16,
-                           pb + h + n16 * 16, (int)tail);
-    else
-        hipLaunchKernelGGL(zero_path_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(pb + h), n16,
-                           pb + h + n16 * 16, (int)tail);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    return ALIGNER_OK;
+    if (flags & ALIGNER_F_STREAM_PATH) return launch_zero_path<true>((unsigned)blocks, pb + h, n16, pb + h + n16 * 16, (int)tail, s);
+    return launch_zero_path<false>((unsigned)blocks, pb + h, n16, pb + h + n16 * 16, (int)tail, s);
 }
 
 int aligner_maxpath_scatter_path(const void *ws, void *path, int path_dtype, int B, int Tx, int Ty, void *stream) {
     if (!ws || !path) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (int rc = check_shape(B, Tx, Ty)) return rc;
     if (B == 0) return ALIGNER_OK;
     if (B > 65535) return fail(ALIGNER_EDOM, "grid too large");
     if ((size_t)(Tx + 1) * sizeof(int) > (size_t)device_lds_limit()) return fail(ALIGNER_EDOM, "Tx=%d too large", Tx);
-    const WsLayout L = ws_layout(B, Tx, Ty);
-    const int *starts = reinterpret_cast<const int *>(static_cast<const unsigned char *>(ws) + L.starts_off);
+    const int *starts = ws_starts(ws, B, Tx, Ty);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (path_dtype) {
-        case ALIGNER_DT_F32: return launch_scatter<float>(starts, path, B, Tx, Ty, 1.0f, s);
-        case ALIGNER_DT_F64: return launch_scatter<double>(starts, path, B, Tx, Ty, 1.0, s);
-        case ALIGNER_DT_I32: return launch_scatter<int32_t>(starts, path, B, Tx, Ty, 1, s);
-        case ALIGNER_DT_I64: return launch_scatter<int64_t>(starts, path, B, Tx, Ty, 1, s);
-        case ALIGNER_DT_U8:  return launch_scatter<uint8_t>(starts, path, B, Tx, Ty, 1, s);
-        case ALIGNER_DT_F16: return launch_scatter<uint16_t>(starts, path, B, Tx, Ty, 0x3C00, s);
-        case ALIGNER_DT_BF16: return launch_scatter<uint16_t>(starts, path, B, Tx, Ty, 0x3F80, s);
-        default: return fail(ALIGNER_EINVAL, "path dtype %d not supported", path_dtype);
-    }
+    return with_path_one(path_dtype, [&](auto one) { return launch_scatter(starts, path, B, Tx, Ty, one, s); });
 }
 
 int aligner_maxpath_expand(const void *ws, void *path, int path_dtype, int B, int Tx, int Ty,
@@ -2270,30 +2378,18 @@ int aligner_maxpath(const void *value, int value_dtype, const void *mask, int ma
                     const int32_t *t_ys, void *path_out, int path_dtype, int32_t *tok_out,
                     int32_t *dur_out, void *ws, size_t ws_bytes, int B, int Tx, int Ty,
                     float max_neg_val, int flags, void *stream) {
-    if (path_out && dtype_size(path_dtype) == 0)
-        return fail(ALIGNER_EINVAL, "path dtype %d not supported", path_dtype);
-    // ALIGNER_F_PATH_PREZEROED: the search kernel itself writes the ones into the caller's zeros -- no expand launch
-    // and without it the pipelined kernel's own zero workgroups do the whole path where they can (path_done)
-    const bool prez = path_out && (flags & ALIGNER_F_PATH_PREZEROED);
-    bool path_done = false;
-    int rc = forward_impl(value, value_dtype, mask, mask_dtype, t_xs, t_ys, tok_out, dur_out, ws, ws_bytes, B, Tx, Ty,
-                          max_neg_val, flags, static_cast<hipStream_t>(stream), path_out, path_dtype, prez, &path_done);
-    if (rc || !path_out || B == 0 || path_done) return rc;
-    return aligner_maxpath_expand_ex(ws, path_out, path_dtype, B, Tx, Ty, flags, stream);
+    if (int rc = check_path_dtype(path_out, path_dtype)) return rc;
+    return search_and_path(value, value_dtype, mask, mask_dtype, t_xs, t_ys, path_out, path_dtype, tok_out, dur_out, ws, ws_bytes,
+                           B, Tx, Ty, max_neg_val, flags, stream, 0);
 }
 
 int aligner_maxpath_ld(const void *value, int value_dtype, int ld_value, const int32_t *t_xs, const int32_t *t_ys,
                        void *path_out, int path_dtype, int32_t *tok_out, int32_t *dur_out, void *ws, size_t ws_bytes, int B,
                        int Tx, int Ty, float max_neg_val, int flags, void *stream) {
-    if (path_out && dtype_size(path_dtype) == 0)
-        return fail(ALIGNER_EINVAL, "path dtype %d not supported", path_dtype);
+    if (int rc = check_path_dtype(path_out, path_dtype)) return rc;
     if (flags & ALIGNER_F_STRICT_MASK) return fail(ALIGNER_EINVAL, "aligner_maxpath_ld takes no mask");
-    const bool prez = path_out && (flags & ALIGNER_F_PATH_PREZEROED);
-    bool path_done = false;
-    int rc = forward_impl(value, value_dtype, nullptr, 0, t_xs, t_ys, tok_out, dur_out, ws, ws_bytes, B, Tx, Ty, max_neg_val,
-                          flags, static_cast<hipStream_t>(stream), path_out, path_dtype, prez, &path_done, ld_value);
-    if (rc || !path_out || B == 0 || path_done) return rc;
-    return aligner_maxpath_expand_ex(ws, path_out, path_dtype, B, Tx, Ty, flags, stream);
+    return search_and_path(value, value_dtype, nullptr, 0, t_xs, t_ys, path_out, path_dtype, tok_out, dur_out, ws, ws_bytes,
+                           B, Tx, Ty, max_neg_val, flags, stream, ld_value);
 }
 
 int aligner_maxpath_f32(const float *value, const void *mask, int mask_dtype, const int32_t *t_xs,
@@ -2316,7 +2412,7 @@ int aligner_maxpath_read_status(void *ws, int32_t *status_host, void *stream) {
 int aligner_maxpath_host_f32(int32_t *paths, float *values, const int32_t *t_xs,
                              const int32_t *t_ys, int B, int Tx, int Ty, float max_neg_val, int flags) {
     if (!paths || !values || !t_xs || !t_ys) return fail(ALIGNER_EINVAL, "null pointer");
-    if (B < 0 || Tx < 1 || Ty < 1) return fail(ALIGNER_EINVAL, "bad shape B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if (int rc = check_shape(B, Tx, Ty)) return rc;
     if (B == 0) return ALIGNER_OK;
     if (!(flags & ALIGNER_F_COMPAT_TXGTTY))
         for (int b = 0; b < B; ++b)

@@ -899,3 +899,46 @@ def test_workspace_regrowth_keeps_the_status_word(dev):
     assert aligner_amd.read_status(dev) & 1
     assert aligner_amd.read_status(dev) == 0
     aligner_amd.maxpath.release_workspaces(dev, s.cuda_stream)
+
+
+_PLAN_TY = {40: (64, 61), 100: (128, 125), 200: (256, 253), 400: (448, 445)}          # a multiple of 8 (16-byte loaders); odd
+_PLAN_CASES = [(dt, mask, Tx, Ty, want_path, {})
+               for dt in ("float32", "bfloat16", "float16") for mask in ("none", "prefix", "half")
+               for Tx in _PLAN_TY for Ty in _PLAN_TY[Tx] for want_path in (True, False)]
+_PLAN_CASES += [(dt, mask, 260, 288, True, {"cus_per_utterance": 2})
+                for dt in ("float32", "bfloat16", "float16") for mask in ("none", "half")]
+_PLAN_CASES += [(dt, mask, Tx, Tx + 8, True, {"force_generic": True})
+                for dt in ("float32", "bfloat16", "float16") for mask in ("none", "half") for Tx in (300, 600, 1100)]
+
+
+@pytest.mark.parametrize("dt,mask,Tx,Ty,want_path,kw", _PLAN_CASES,
+                         ids=["%s-%s-%dx%d-%s%s" % (c[0], c[1], c[2], c[3], "path" if c[4] else "nopath", "".join("-" + k for k in c[5]))
+                              for c in _PLAN_CASES])
+def test_every_branch_of_the_launch_plan_vs_oracle(dev, dt, mask, Tx, Ty, want_path, kw):
+    """Every branch of the host side's plan (maxpath.hip, plan_search) at B = 3 with ragged lengths: the wave tiers (Tx 40,
+    100, 200, 400), 16-byte and 4-byte loaders (Ty a multiple of 8; odd -- 16-bit scores then take the generic kernel), no
+    mask, a strict all-ones prefix mask and one with a 0.5 inside the rectangle (verified in front without a path,
+    optimistic + redo with one, multiplied on eight waves), the dense path in the launch or not asked for; the
+    two-workgroup form and the generic kernel's four sizes.  Bit for bit against the oracle on the fp32 up-cast of what
+    torch computes as value * mask in that dtype."""
+    import aligner_amd
+    B, dt = 3, getattr(torch, dt)
+    rng = np.random.default_rng(Tx * 4099 + Ty)
+    v = torch.from_numpy(rng.standard_normal((B, Tx, Ty)).astype(np.float32) * 3).to(dt)
+    ty = rng.integers(Tx, Ty + 1, B).astype(np.int32)
+    tx = np.array([rng.integers(1, Tx + 1) for _ in ty], np.int32)
+    tx[0], ty[0] = Tx, Ty
+    m = None
+    if mask != "none":
+        m = torch.from_numpy(synth.prefix_mask(tx, ty, Tx, Ty)).to(dt)
+        if mask == "half":
+            m[B - 1, tx[B - 1] // 2, ty[B - 1] // 2] = 0.5       # inside the last utterance's rectangle
+    want = _oracle_path((v if m is None else v * m).float().numpy(), tx, ty)
+    r = aligner_amd.align(v.to(dev), torch.from_numpy(tx).to(dev), torch.from_numpy(ty).to(dev),
+                          mask=None if m is None else m.to(dev), strict_mask=m is not None, want_path=want_path,
+                          path_dtype=torch.int32, want_tok=True, want_durations=True, **kw)
+    torch.cuda.synchronize()
+    if want_path:
+        assert np.array_equal(r.path.cpu().numpy(), want)
+    _check_consistency(want, r.tok.cpu().numpy(), r.durations.cpu().numpy(), tx, ty)
+    assert aligner_amd.read_status(dev) == 0
