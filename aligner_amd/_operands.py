@@ -3,6 +3,7 @@ the current stream's handle, the per-utterance lengths, and the checks of the Ga
 The C-ABI calls themselves stay written out in their modules."""
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -66,3 +67,47 @@ def one_gpu(named, names: str) -> torch.device:
     if any(t.device != dev for t, _ in named):
         raise ValueError(f"{names} must be on the same device")
     return dev
+
+
+def dp_parameters(gamma, warp_penalty) -> Tuple[float, float]:
+    """Soft-DTW's (gamma, warp_penalty) as floats, checked."""
+    gamma, warp_penalty = float(gamma), float(warp_penalty)
+    if not (gamma > 0.0 and math.isfinite(gamma)):
+        raise ValueError("gamma must be positive and finite")
+    if not (warp_penalty >= 0.0 and math.isfinite(warp_penalty)):
+        raise ValueError("warp_penalty must be finite and not negative")
+    return gamma, warp_penalty
+
+
+def pred_target_shapes(pred, target, scale) -> Tuple[int, int, int, int, float]:
+    """(B, C, N, M, scale) of the L1 cost's pred [B,C,N] and target [B,C,M], checked."""
+    for t, name in ((pred, "pred"), (target, "target")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{name} must be a [B,C,T] tensor")
+        if not t.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point tensor")
+    B, C, N = pred.shape
+    if target.shape[0] != B or target.shape[1] != C:
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} disagree in B or C")
+    if C < 1:
+        raise ValueError("C must be at least 1")
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("scale must be finite")
+    return B, C, N, target.shape[2], scale
+
+
+def check_reduction(reduction: str) -> None:
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+
+
+def reduced(value: torch.Tensor, reduction: str, zero_infinity: bool) -> torch.Tensor:
+    """The per-utterance losses reduced: "mean", "sum" or "none"; zero_infinity: +inf (no alignment) counts as 0."""
+    if zero_infinity:
+        value = torch.where(torch.isinf(value), torch.zeros_like(value), value)
+    if reduction == "mean":
+        return value.mean()
+    if reduction == "sum":
+        return value.sum()
+    return value

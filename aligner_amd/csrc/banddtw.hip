@@ -1,0 +1,591 @@
+// Soft-DTW in band storage (include/aligner_amd.h has the definition): cost, R and E are [B,N,W],
+// W = 2w + 1, element [i,d] is cell (i, j = i + d - w).  Memory is O(N w) and N has no limit of its own; the cell
+// arithmetic is softdtw_cell.h's, shared with the dense kernels.
+//
+// The DP.  One workgroup per utterance, and one wave of it walks the anti-diagonals s = i + j, one a step.  With
+// o = w & 1 and dd = d + o, a cell sits in column c = dd >> 1 (0 .. w) and slot q = dd & 1 of the band, and on
+// anti-diagonal s exactly the cells with q = s & 1 are present: one per column.  Lane l owns column l, and for
+// w > 63 column 64 + l as well -- two independent cells a step in one wave, which fill each other's latencies,
+// where two waves would need a hand-off and a barrier a step.  The predecessors of (c,q) are (c,q) itself two steps
+// back, and one step back (c,1) and (c-1,1) for q = 0, (c,0) and (c+1,0) for q = 1: the lane's own registers and
+// one DPP move from a neighbour lane (column 63 <-> 64: a readlane into the move's edge value).  No LDS, no barrier
+// and no other wave on the dependent chain.
+//
+// Staging.  A tile is BD_T = 32 steps.  In memory the cells of a tile are, for each row i, the BD_T consecutive
+// floats d = s0 + w - 2 i + t (t = 0 .. 31): 128-byte segments, two rows per wave load, issued for the next tile
+// before the current tile's steps.  In LDS the tile is [t][column] at a pitch of PITCH = NC + 16 floats
+// (NC = 64 or 128 columns), so a step reads lane-linear addresses.  The movers' store has lane t of a row at
+// t PITCH + c0 + (t >> 1); PITCH = 16 (mod 32), so even t = 2k fall on bank c0 + k and odd t = 2k + 1 on bank
+// c0 + k + 16: the 32 lanes of a row (an LDS store is served 32 lanes at a time, on 32 banks) hit 32 banks.
+// R leaves the forward kernel through the same tile.
+//
+// Backward never reads the costs: it sweeps the tiles in reverse over the stored R (two tiles resident in an LDS
+// ring, since a cell needs R one and two steps back, columns c - 1 .. c + 1 read straight from LDS, off the chain),
+// and pushes E with the softmin's own weights; the chain is two additions, a DPP move and two products a step.
+// E overwrites R in place.  Waves 1 .. 3 of the backward workgroup only write the exact zeros of the elements
+// without a cell and leave; wave 0 sweeps.
+//
+// The L1 cost and its gradient in the same layout follow the kernels of l1cost.hip: formulas, sign(0) = 0, one owner
+// per output element, a fixed order of summation, G selected (never multiplied) by "the cell exists".
+#include "common.h"
+#include "device.h"
+#include "softdtw_cell.h"
+
+namespace aligner {
+
+constexpr int BD_T = 32;                    // steps per tile
+constexpr int BD_MAX_W = 127;
+constexpr int BD_BWD_WAVES = 4;             // backward: wave 0 sweeps, the others write zeros
+constexpr int BD_MAX_C = 4096;
+constexpr int BC_RB = 16;                   // rows per wave tile of the cost kernel
+constexpr int BC_CC = 8;                    // channels per wave (gradients)
+constexpr int BC_TR = 8;                    // rows per step (dtarget)
+constexpr int BC_PR = 8;                    // rows per wave (dpred): BC_PR * BC_CC == 64 sums
+constexpr int BC_PITCH = 65;
+
+struct BandDtwParams {
+    const float *cost;      // [B,N,W]
+    const int   *ns, *ms;   // [B] or null
+    float scale, pen, unscale;
+    int   w;
+    float *value;           // [B]
+    float *grad;            // [B,N,W]: R (scaled) after forward, E after backward; null: value only
+    float *fin;             // workspace [B]
+    int B, N;
+};
+
+__device__ __forceinline__ bool bd_lengths(const BandDtwParams &p, int b, int &n, int &m) {
+    n = p.ns ? p.ns[b] : p.N;
+    m = p.ms ? p.ms[b] : p.N;
+    n = n < p.N ? n : p.N;
+    m = m < p.N + p.w ? m : p.N + p.w;
+    if (n < 1 || m < 1) return false;
+    const int d = n > m ? n - m : m - n;
+    return d <= p.w;
+}
+
+// A lane's view of one of its cells (column c, slot q): the rows [ia, ia + len) on which the cell exists
+struct BdSlot { int ia; unsigned len; };
+__device__ __forceinline__ BdSlot bd_slot(int c, int q, int w, int wp, int n, int m) {
+    const int d = 2 * c + q - (wp - w);
+    const int e = wp - 2 * c - q;                             // i - j
+    int ia = e > 0 ? e : 0;                                   // j >= 0
+    int ib = m + e < n ? m + e : n;                           // j < m
+    if (d < 0 || d > 2 * w || ib < ia) ib = ia;
+    BdSlot s;
+    s.ia = ia;
+    s.len = (unsigned)(ib - ia);
+    return s;
+}
+
+// The movers' element k of tile s0: row rtop + 2 k + (lane >> 5), step t = lane & 31; column c, band index d.
+// NC columns and BD_T steps: every (t, c) of the tile belongs to exactly one (k, lane).
+template <int NC> struct BdMover {
+    static constexpr int NK = (NC + BD_T / 2) / 2;
+    int row0, c0, d0, t;
+    __device__ __forceinline__ BdMover(int s0, int w, int wp, int lane) {
+        const int hb = (s0 + wp) >> 1;                        // (s0 + wp is even; arithmetic shift for tile -1)
+        t = lane & 31;
+        row0 = hb - (NC - 1) + (lane >> 5);
+        c0 = hb - row0 + (t >> 1);
+        d0 = 2 * c0 + (t & 1) - (wp - w);
+    }
+    __device__ __forceinline__ int row(int k) const { return row0 + 2 * k; }
+    __device__ __forceinline__ int col(int k) const { return c0 - 2 * k; }
+    __device__ __forceinline__ int d(int k) const { return d0 - 4 * k; }
+    // element k is a cell that exists (then its column is in [0, NC) as well); off: its place in the utterance's block
+    __device__ __forceinline__ bool cell(int k, int n, int m, int w, int &off) const {
+        const int r = row(k), dk = d(k), j = r + dk - w;
+        off = r * (2 * w + 1) + dk;
+        return r >= 0 && r < n && dk >= 0 && dk <= 2 * w && j >= 0 && j < m;
+    }
+    __device__ __forceinline__ bool staged(int k) const { return col(k) >= 0 && col(k) < NC; }
+    __device__ __forceinline__ int lds(int k, int pitch) const { return t * pitch + col(k); }
+};
+
+template <int NC>
+__global__ __launch_bounds__(64) void banddtw_forward_kernel(BandDtwParams p) {
+    constexpr int PITCH = NC + 16, NP = NC / 64, NK = BdMover<NC>::NK;
+    __shared__ float tile[BD_T * PITCH];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int n, m;
+    if (!bd_lengths(p, b, n, m)) {
+        if (lane == 0) { p.value[b] = __builtin_huge_valf(); p.fin[b] = SD_BIG; }
+        return;
+    }
+    const int w = p.w, W = 2 * w + 1, wp = w + (w & 1);
+    const size_t ubase = (size_t)b * p.N * W;
+    const float *cost = p.cost + ubase;
+    float *R = p.grad ? p.grad + ubase : nullptr;
+    const int slast = n + m - 2, ntl = slast / BD_T + 1;
+    BdSlot sl[NP][2];
+    float x[NP][2];                                           // the lane's cells as of their last step
+#pragma unroll
+    for (int a = 0; a < NP; ++a)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            sl[a][q] = bd_slot(64 * a + lane, q, w, wp, n, m);
+            x[a][q] = (q == 0 && 2 * (64 * a + lane) == wp) ? 0.f : SD_BIG;      // R[-1,-1] = 0, two steps before (0,0)
+        }
+    float v[NK];
+    auto load = [&](int tl) {
+        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            int off;
+            float c = SD_BIG;
+            if (mv.cell(k, n, m, w, off)) c = cost[off];
+            v[k] = sd_cost_in(c, p.scale);
+        }
+    };
+    auto stage = [&](int tl) {
+        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            if (mv.staged(k)) tile[mv.lds(k, PITCH)] = v[k];
+        }
+    };
+    load(0);
+    stage(0);
+    sd_wave_lds_sync();
+    for (int tl = 0; tl < ntl; ++tl) {
+        if (tl + 1 < ntl) load(tl + 1);
+        const int hb = (tl * BD_T + wp) >> 1;
+        int rel[NP][2];                                       // row of the slot's cell at t = 0 or 1, from ia
+#pragma unroll
+        for (int a = 0; a < NP; ++a)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) rel[a][q] = hb - (64 * a + lane) - sl[a][q].ia;
+#pragma unroll 1
+        for (int t8 = 0; t8 < BD_T; t8 += 8) {
+            float dv[8][NP];
+#pragma unroll
+            for (int tt = 0; tt < 8; ++tt)
+#pragma unroll
+                for (int a = 0; a < NP; ++a) dv[tt][a] = tile[(t8 + tt) * PITCH + 64 * a + lane];
+#pragma unroll
+            for (int tt = 0; tt < 8; ++tt) {
+                const int q = tt & 1, u = (t8 + tt) >> 1;
+                float nb[NP];                                 // the neighbour column's cell of the step before
+                if (q == 0) {                                 // (c-1, 1)
+                    nb[0] = sd_from_below(SD_BIG, x[0][1]);
+                    if (NP == 2) nb[NP - 1] = sd_from_below(sd_lane(x[0][1], 63), x[NP - 1][1]);
+                } else {                                      // (c+1, 0)
+                    nb[NP - 1] = sd_from_above(SD_BIG, x[NP - 1][0]);
+                    if (NP == 2) nb[0] = sd_from_above(sd_lane(x[NP - 1][0], 0), x[0][0]);
+                }
+#pragma unroll
+                for (int a = 0; a < NP; ++a) {
+                    const float up = q == 0 ? x[a][1] : nb[a], left = q == 0 ? nb[a] : x[a][0];
+                    float cur = sd_cell(x[a][q], up, left, p.pen, dv[tt][a]);
+                    cur = (unsigned)(rel[a][q] + u) < sl[a][q].len ? cur : SD_BIG;
+                    x[a][q] = cur;
+                    tile[(t8 + tt) * PITCH + 64 * a + lane] = cur;
+                }
+            }
+        }
+        sd_wave_lds_sync();
+        if (tl == ntl - 1) {                                  // cell (n-1, m-1): step slast, e = n - m
+            const int dd = wp - (n - m);
+            const float fin = tile[(slast - tl * BD_T) * PITCH + (dd >> 1)];
+            if (lane == 0) {
+                p.fin[b] = fin;
+                p.value[b] = fin < 0.5f * SD_BIG ? fin * p.unscale : __builtin_huge_valf();
+            }
+        }
+        if (R) {
+            const BdMover<NC> mv(tl * BD_T, w, wp, lane);
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                int off;
+                if (mv.cell(k, n, m, w, off)) R[off] = tile[mv.lds(k, PITCH)];
+            }
+            sd_wave_lds_sync();
+        }
+        if (tl + 1 < ntl) {
+            stage(tl + 1);
+            sd_wave_lds_sync();
+        }
+    }
+}
+
+template <int NC>
+__global__ __launch_bounds__(64 * BD_BWD_WAVES) void banddtw_backward_kernel(BandDtwParams p) {
+    constexpr int PITCH = NC + 16, NP = NC / 64, NK = BdMover<NC>::NK;
+    static_assert(NC + 2 <= PITCH, "columns -1 and NC");
+    __shared__ float ring[2 * BD_T * PITCH];                  // [step & 63][column + 1]
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int n, m;
+    const bool some = bd_lengths(p, b, n, m) && p.fin[b] < 0.5f * SD_BIG;
+    const int w = p.w, W = 2 * w + 1, wp = w + (w & 1);
+    float *E = p.grad + (size_t)b * p.N * W;
+    if (wv > 0 || !some) {
+        // exact zeros where no cell exists (the sweep writes every cell that does), everywhere without an alignment
+        for (int r = some ? wv - 1 : wv; r < p.N; r += some ? BD_BWD_WAVES - 1 : BD_BWD_WAVES) {
+            int lo = 0, hi = 0;                               // the row's cells: d in [lo, hi)
+            if (some && r < n) {
+                lo = w - r > 0 ? w - r : 0;
+                hi = m - r + w < W ? m - r + w : W;
+                hi = hi > lo ? hi : lo;
+            }
+            for (int d = lane; d < W; d += 64)
+                if (d < lo || d >= hi) E[r * W + d] = 0.f;
+        }
+        return;
+    }
+    const int slast = n + m - 2, ntl = slast / BD_T + 1;
+    for (int k = lane; k < 2 * BD_T * PITCH; k += 64) ring[k] = SD_BIG;
+    BdSlot sl[NP][2];
+    int finrel[NP][2];                                        // the slot's row n - 1 from ia where it is cell (n-1, m-1)
+    float pd[NP][2], pu[NP][2], pl[NP][2];                    // what the slot's last cell handed to (i-1,j-1), (i-1,j), (i,j-1)
+    const int ddfin = wp - (n - m);
+#pragma unroll
+    for (int a = 0; a < NP; ++a)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            sl[a][q] = bd_slot(64 * a + lane, q, w, wp, n, m);
+            finrel[a][q] = 2 * (64 * a + lane) + q == ddfin ? n - 1 - sl[a][q].ia : -0x40000000;
+            pd[a][q] = pu[a][q] = pl[a][q] = 0.f;
+        }
+    float v[NK];
+    auto load = [&](int tl) {
+        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            int off;
+            float r = (mv.row(k) == -1 && mv.d(k) == w) ? 0.f : SD_BIG;       // R[-1,-1] = 0
+            if (mv.cell(k, n, m, w, off)) r = E[off];
+            v[k] = r;
+        }
+    };
+    auto stage = [&](int tl) {
+        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
+        float *half = ring + (tl & 1) * BD_T * PITCH + 1;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            if (mv.staged(k)) half[mv.lds(k, PITCH)] = v[k];
+        }
+    };
+    sd_wave_lds_sync();
+    load(ntl - 1);
+    stage(ntl - 1);
+    load(ntl - 2);
+    stage(ntl - 2);
+    sd_wave_lds_sync();
+    for (int tl = ntl - 1; tl >= 0; --tl) {
+        if (tl - 2 >= -1) load(tl - 2);
+        float *cur = ring + (tl & 1) * BD_T * PITCH + 1, *oth = ring + ((tl & 1) ^ 1) * BD_T * PITCH + 1;
+        const int hb = (tl * BD_T + wp) >> 1;
+        int rel[NP][2];
+#pragma unroll
+        for (int a = 0; a < NP; ++a)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) rel[a][q] = hb - (64 * a + lane) - sl[a][q].ia;
+#pragma unroll 1
+        for (int t4 = BD_T - 4; t4 >= 0; t4 -= 4) {
+            // the three stored predecessors of each cell, read up front: rows t-1 and t-2 of the ring (the other
+            // half's last rows for t = 0, 1), not yet overwritten by E
+            float rd[4][NP], ru[4][NP], rl[4][NP];
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) {
+                const int t = t4 + tt, q = tt & 1;
+                const float *r1 = t >= 1 ? cur + (t - 1) * PITCH : oth + (BD_T - 1) * PITCH;
+                const float *r2 = t >= 2 ? cur + (t - 2) * PITCH : oth + (BD_T - 2 + t) * PITCH;
+#pragma unroll
+                for (int a = 0; a < NP; ++a) {
+                    const int c = 64 * a + lane;
+                    rd[tt][a] = r2[c];
+                    ru[tt][a] = r1[q == 0 ? c : c + 1];
+                    rl[tt][a] = r1[q == 0 ? c - 1 : c];
+                }
+            }
+#pragma unroll
+            for (int tt = 3; tt >= 0; --tt) {
+                const int t = t4 + tt, q = tt & 1, u = t >> 1;
+                float nb[NP];                                 // the neighbour column's push of the step before
+                if (q == 0) {                                 // from (c-1, 1) = (i+1, j): its push upwards
+                    nb[0] = sd_from_below(0.f, pu[0][1]);
+                    if (NP == 2) nb[NP - 1] = sd_from_below(sd_lane(pu[0][1], 63), pu[NP - 1][1]);
+                } else {                                      // from (c+1, 0) = (i, j+1): its push to the left
+                    nb[NP - 1] = sd_from_above(0.f, pl[NP - 1][0]);
+                    if (NP == 2) nb[0] = sd_from_above(sd_lane(pl[NP - 1][0], 0), pl[0][0]);
+                }
+#pragma unroll
+                for (int a = 0; a < NP; ++a) {
+                    const float inl = q == 0 ? pl[a][1] : nb[a], inu = q == 0 ? nb[a] : pu[a][0];
+                    float e = inl + (inu + pd[a][q]);
+                    const int r = rel[a][q] + u;
+                    if (r == finrel[a][q]) e = 1.f;
+                    e = (unsigned)r < sl[a][q].len ? e : 0.f;
+                    sd_push(rd[tt][a], ru[tt][a], rl[tt][a], p.pen, e, pd[a][q], pu[a][q], pl[a][q]);
+                    cur[t * PITCH + 64 * a + lane] = e;
+                }
+            }
+        }
+        sd_wave_lds_sync();
+        {
+            const BdMover<NC> mv(tl * BD_T, w, wp, lane);
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                int off;
+                if (mv.cell(k, n, m, w, off)) E[off] = cur[mv.lds(k, PITCH)];
+            }
+        }
+        sd_wave_lds_sync();
+        if (tl - 2 >= -1) {
+            stage(tl - 2);
+            sd_wave_lds_sync();
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the L1 cost in band storage and its gradient
+
+__device__ __forceinline__ float bc_signed(float p, float t, float g) { return p > t ? g : (p < t ? -g : 0.f); }
+__device__ __forceinline__ float bc_lane(float v, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+
+// A wave owns rows i0 .. i0 + 15 and the 64 columns j = i0 - w + 64 ct + lane: one target load per channel feeds
+// 16 cells, and row i0 + r stores d = 64 ct + lane - r, contiguous over the lanes.
+__global__ __launch_bounds__(256) void band_l1_cost_kernel(
+        const float *__restrict__ pred, const float *__restrict__ target, const int *__restrict__ ns,
+        const int *__restrict__ ms, int w, float scale, float *__restrict__ cost, int C, int N, int M, int nch) {
+    const int b = blockIdx.z, lane = threadIdx.x & 63;
+    const int inner = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ct = inner % nch, i0 = (inner / nch) * BC_RB, W = 2 * w + 1;
+    if (i0 >= N) return;
+    const int n = clamp_len(ns, b, N);
+    int m = clamp_len(ms, b, M);
+    m = m < N + w ? m : N + w;
+    const int j = i0 - w + 64 * ct + lane;
+    float acc[BC_RB];
+#pragma unroll
+    for (int r = 0; r < BC_RB; ++r) acc[r] = 0.f;
+    // (wave-uniform) the tile has a cell: a row below n, a column in [0, m)
+    const int jfirst = i0 - w + 64 * ct;
+    if (i0 < n && jfirst < m && jfirst + 63 >= 0) {
+        const float *t = target + (size_t)b * C * M + (j < 0 ? 0 : (j < M ? j : M - 1));
+        const float *p = pred + (size_t)b * C * N + (i0 + lane < N ? i0 + lane : N - 1);
+        for (int c = 0; c < C; ++c, t += M, p += N) {
+            const float tv = *t, pl = *p;
+#pragma unroll
+            for (int r = 0; r < BC_RB; ++r) acc[r] = acc[r] + __builtin_fabsf(tv - bc_lane(pl, r));
+        }
+    }
+    float *out = cost + ((size_t)b * N + i0) * W;
+#pragma unroll
+    for (int r = 0; r < BC_RB; ++r) {
+        const int i = i0 + r, d = 64 * ct + lane - r;
+        if (i < N && d >= 0 && d < W) out[r * W + d] = (i < n && j >= 0 && j < m) ? acc[r] * scale : 0.f;
+    }
+}
+
+// dtarget: a wave owns 64 columns and BC_CC channels and walks the rows j0 - w .. j0 + 63 + w; lane j reads
+// G[i, j - i + w], contiguous over the lanes.
+__global__ __launch_bounds__(256) void band_l1_dtarget_kernel(
+        const float *__restrict__ G, const float *__restrict__ pred, const float *__restrict__ target,
+        const int *__restrict__ ns, const int *__restrict__ ms, int w, float scale, const float *__restrict__ row_scale,
+        float *__restrict__ dtarget, int C, int N, int M) {
+    const int b = blockIdx.z, lane = threadIdx.x & 63, W = 2 * w + 1;
+    const int c0 = (blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * BC_CC;
+    const int j0 = blockIdx.x * 64, j = j0 + lane;
+    if (c0 >= C) return;
+    const int n = clamp_len(ns, b, N);
+    int m = clamp_len(ms, b, M);
+    m = m < N + w ? m : N + w;
+    const int cmax = (c0 + BC_CC < C ? c0 + BC_CC : C) - 1 - c0;
+    float acc[BC_CC];
+#pragma unroll
+    for (int cc = 0; cc < BC_CC; ++cc) acc[cc] = 0.f;
+    const int jlast = (j0 + 64 < m ? j0 + 64 : m) - 1;
+    const int ilo = j0 - w > 0 ? j0 - w : 0;
+    const int ihi = jlast + w + 1 < n ? jlast + w + 1 : n;
+    if (j0 < m && ilo < ihi) {
+        const float *t = target + ((size_t)b * C + c0) * M + (j < M ? j : M - 1);
+        const float *p = pred + ((size_t)b * C + c0) * N;
+        const float *g = G + (size_t)b * N * W;
+        float tv[BC_CC];
+#pragma unroll
+        for (int cc = 0; cc < BC_CC; ++cc) tv[cc] = t[(size_t)(cc < cmax ? cc : cmax) * M];
+        for (int ib = ilo; ib < ihi; ib += BC_TR) {
+            float gv[BC_TR];
+#pragma unroll
+            for (int r = 0; r < BC_TR; ++r) {
+                const int i = ib + r, d = j - i + w;
+                const bool ok = i < ihi && j < m && d >= 0 && d < W;
+                gv[r] = and_mask(g[(i < N ? i : N - 1) * W + (d < 0 ? 0 : (d < W ? d : W - 1))], ok ? ~0u : 0u);
+            }
+            const int rl = ib + lane < N ? ib + lane : N - 1;
+#pragma unroll
+            for (int cc = 0; cc < BC_CC; ++cc) {
+                const float pl = p[(size_t)(cc < cmax ? cc : cmax) * N + rl];
+#pragma unroll
+                for (int r = 0; r < BC_TR; ++r) acc[cc] = acc[cc] + bc_signed(bc_lane(pl, r), tv[cc], gv[r]);
+            }
+        }
+    }
+    if (j >= M) return;
+    const float k = -(scale * (row_scale ? row_scale[b] : 1.f));
+    float *out = dtarget + ((size_t)b * C + c0) * M + j;
+#pragma unroll
+    for (int cc = 0; cc < BC_CC; ++cc)
+        if (cc <= cmax) out[(size_t)cc * M] = j < m && n > 0 ? acc[cc] * k : 0.f;
+}
+
+// dpred: a wave owns BC_PR rows and BC_CC channels; lane l sums the cells d = l, l + 64, ... of each row (G and
+// target both contiguous over the lanes), and the 64 lanes' sums meet in LDS, added in lane order.
+__global__ __launch_bounds__(64) void band_l1_dpred_kernel(
+        const float *__restrict__ G, const float *__restrict__ pred, const float *__restrict__ target,
+        const int *__restrict__ ns, const int *__restrict__ ms, int w, float scale, const float *__restrict__ row_scale,
+        float *__restrict__ dpred, int C, int N, int M) {
+    __shared__ float red[64 * BC_PITCH];
+    const int b = blockIdx.z, lane = threadIdx.x, W = 2 * w + 1;
+    const int i0 = blockIdx.x * BC_PR, c0 = blockIdx.y * BC_CC;
+    const int n = clamp_len(ns, b, N);
+    int m = clamp_len(ms, b, M);
+    m = m < N + w ? m : N + w;
+    const int cmax = (c0 + BC_CC < C ? c0 + BC_CC : C) - 1 - c0;
+    const int oc = lane / BC_PR, oi = i0 + lane % BC_PR;
+    float *out = dpred + ((size_t)b * C + c0 + oc) * N + oi;
+    const bool stored = oc <= cmax && oi < N;
+    if (i0 >= n || m < 1) {                                               // (wave-uniform)
+        if (stored) *out = 0.f;
+        return;
+    }
+    float acc[BC_CC][BC_PR];
+#pragma unroll
+    for (int cc = 0; cc < BC_CC; ++cc)
+#pragma unroll
+        for (int r = 0; r < BC_PR; ++r) acc[cc][r] = 0.f;
+    const float *tb = target + ((size_t)b * C + c0) * M;
+    const float *pb = pred + ((size_t)b * C + c0) * N;
+    const float *gb = G + (size_t)b * N * W;
+    for (int dc = 0; dc < W; dc += 64) {
+        const int d = dc + lane;
+#pragma unroll
+        for (int r = 0; r < BC_PR; ++r) {
+            const int i = i0 + r, j = i + d - w;
+            const bool ok = i < n && d < W && j >= 0 && j < m;
+            const float gv = and_mask(gb[(i < N ? i : N - 1) * W + (d < W ? d : W - 1)], ok ? ~0u : 0u);
+            const int jc = j < 0 ? 0 : (j < M ? j : M - 1);
+#pragma unroll
+            for (int cc = 0; cc < BC_CC; ++cc) {
+                const int ch = cc < cmax ? cc : cmax;
+                const float pv = pb[(size_t)ch * N + (i < N ? i : N - 1)];
+                acc[cc][r] = acc[cc][r] + bc_signed(pv, tb[(size_t)ch * M + jc], gv);
+            }
+        }
+    }
+#pragma unroll
+    for (int cc = 0; cc < BC_CC; ++cc)
+#pragma unroll
+        for (int r = 0; r < BC_PR; ++r) red[(cc * BC_PR + r) * BC_PITCH + lane] = acc[cc][r];
+    __syncthreads();
+    float sum = 0.f;
+#pragma unroll 8
+    for (int x = 0; x < 64; ++x) sum = sum + red[lane * BC_PITCH + x];
+    const float k = scale * (row_scale ? row_scale[b] : 1.f);
+    if (stored) *out = oi < n ? sum * k : 0.f;
+}
+
+static int bd_domain(int B, int N, int bandwidth) {
+    if (bandwidth > BD_MAX_W) return fail(ALIGNER_EDOM, "bandwidth=%d too large (<= %d; the dense calls take any band)", bandwidth, BD_MAX_W);
+    if (B > 65535) return fail(ALIGNER_EDOM, "B=%d too large", B);
+    if ((long long)N * (2 * bandwidth + 1) >= (1ll << 29))
+        return fail(ALIGNER_EDOM, "N*W=%lld too large (< 2^29)", (long long)N * (2 * bandwidth + 1));
+    return ALIGNER_OK;
+}
+
+static int bc_check(int B, int C, int N, int M, float scale, int bandwidth) {
+    if (B < 1 || C < 1 || N < 1 || M < 1) return fail(ALIGNER_EINVAL, "bad shape");
+    if (!(scale == scale) || !(scale < __builtin_huge_valf()) || !(scale > -__builtin_huge_valf()))
+        return fail(ALIGNER_EINVAL, "scale must be finite");
+    if (bandwidth < 0) return fail(ALIGNER_EINVAL, "bandwidth must be at least 0");
+    if (C > BD_MAX_C) return fail(ALIGNER_EDOM, "C=%d too large (<= %d)", C, BD_MAX_C);
+    return bd_domain(B, N, bandwidth);
+}
+
+}  // namespace aligner
+
+using namespace aligner;
+
+extern "C" {
+
+size_t aligner_soft_dtw_banded_workspace_bytes(int B, int N, int bandwidth, int want_grad) {
+    (void)want_grad;                                          // R lives in the gradient buffer: one float per utterance either way
+    if (B < 1 || N < 1 || bandwidth < 0 || bandwidth > BD_MAX_W || B > 65535) return 0;
+    if ((long long)N * (2 * bandwidth + 1) >= (1ll << 29)) return 0;
+    return align_up((size_t)B * sizeof(float), 256);
+}
+
+int aligner_soft_dtw_banded_f32(const float *cost_band, const int32_t *n_dev, const int32_t *m_dev, float gamma,
+                                float warp_penalty, int bandwidth, float *value_out, float *grad_band_out, void *workspace,
+                                size_t workspace_bytes, int B, int N, void *stream) {
+    if (!cost_band || !value_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
+    if (B < 1 || N < 1) return fail(ALIGNER_EINVAL, "bad shape");
+    if (!(gamma > 0.f) || !(gamma < __builtin_huge_valf())) return fail(ALIGNER_EINVAL, "gamma must be positive and finite");
+    if (!(warp_penalty >= 0.f) || !(warp_penalty < __builtin_huge_valf()))
+        return fail(ALIGNER_EINVAL, "warp_penalty must be finite and not negative");
+    if (bandwidth < 0) return fail(ALIGNER_EINVAL, "bandwidth must be at least 0");
+    if (const int rc = bd_domain(B, N, bandwidth)) return rc;
+    const size_t need = aligner_soft_dtw_banded_workspace_bytes(B, N, bandwidth, grad_band_out != nullptr);
+    if (workspace_bytes < need)
+        return fail(ALIGNER_ENOSPC, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BandDtwParams p;
+    p.cost = cost_band; p.ns = n_dev; p.ms = m_dev;
+    const double scale = 1.4426950408889634 / (double)gamma;
+    p.scale = (float)scale;
+    const double pen = (double)warp_penalty * scale;
+    p.pen = pen < (double)SD_BIG ? (float)pen : SD_BIG;
+    p.unscale = (float)((double)gamma * 0.6931471805599453);
+    p.w = bandwidth;
+    p.value = value_out; p.grad = grad_band_out; p.fin = static_cast<float *>(workspace);
+    p.B = B; p.N = N;
+    if (bandwidth <= 63) hipLaunchKernelGGL(banddtw_forward_kernel<64>, dim3(B), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL(banddtw_forward_kernel<128>, dim3(B), dim3(64), 0, s, p);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    if (grad_band_out) {
+        if (bandwidth <= 63) hipLaunchKernelGGL(banddtw_backward_kernel<64>, dim3(B), dim3(64 * BD_BWD_WAVES), 0, s, p);
+        else hipLaunchKernelGGL(banddtw_backward_kernel<128>, dim3(B), dim3(64 * BD_BWD_WAVES), 0, s, p);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    return ALIGNER_OK;
+}
+
+int aligner_l1_cost_banded_f32(const float *pred, const float *target, const int32_t *n_dev, const int32_t *m_dev, int bandwidth,
+                               float scale, float *cost_band_out, int B, int C, int N, int M, void *stream) {
+    if (!pred || !target || !cost_band_out) return fail(ALIGNER_EINVAL, "null pointer");
+    if (const int rc = bc_check(B, C, N, M, scale, bandwidth)) return rc;
+    const int W = 2 * bandwidth + 1, nch = (W + BC_RB - 1 + 63) / 64, nrb = (N + BC_RB - 1) / BC_RB;
+    hipLaunchKernelGGL(band_l1_cost_kernel, dim3((unsigned)(nch * nrb + 3) / 4, 1, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       pred, target, n_dev, m_dev, bandwidth, scale, cost_band_out, C, N, M, nch);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+
+int aligner_l1_cost_banded_backward_f32(const float *grad_band, const float *pred, const float *target, const int32_t *n_dev,
+                                        const int32_t *m_dev, int bandwidth, float scale, const float *row_scale,
+                                        float *dpred_out, float *dtarget_out, int B, int C, int N, int M, void *stream) {
+    if (!grad_band || !pred || !target) return fail(ALIGNER_EINVAL, "null pointer");
+    if (!dpred_out && !dtarget_out) return fail(ALIGNER_EINVAL, "null pointer: no output");
+    if (const int rc = bc_check(B, C, N, M, scale, bandwidth)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nchunks = (C + BC_CC - 1) / BC_CC;
+    if (dpred_out) {
+        hipLaunchKernelGGL(band_l1_dpred_kernel, dim3((N + BC_PR - 1) / BC_PR, nchunks, B), dim3(64), 0, s,
+                           grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dpred_out, C, N, M);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    if (dtarget_out) {
+        hipLaunchKernelGGL(band_l1_dtarget_kernel, dim3((M + 63) / 64, (nchunks + 3) / 4, B), dim3(256), 0, s,
+                           grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dtarget_out, C, N, M);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    return ALIGNER_OK;
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@
 // (i,j) and its three successors are done: E overwrites R in place in the gradient buffer.
 #include "common.h"
 #include "device.h"
+#include "softdtw_cell.h"
 
 namespace aligner {
 
@@ -33,7 +34,6 @@ constexpr int   SD_LAG = (63 + SD_TW - 1) / SD_TW + 1;    // tiles between neigh
 constexpr int   SD_RS = 64 / SD_TW;                       // rows a wave moves per pass of a tile
 constexpr int   SD_RING = 64;                             // hand-off ring of a wave, entries (a column each)
 constexpr int   SD_MAX_N = 1024;
-constexpr float SD_BIG = 1e30f;                           // "+inf" in scaled units
 constexpr int   SD_NO_BAND = 1 << 30;
 
 struct SoftDtwParams {
@@ -48,21 +48,6 @@ struct SoftDtwParams {
     float *fin;             // workspace [B]: R[n-1,m-1] scaled, SD_BIG without an alignment
     int B, N, M;
 };
-
-// lane i <- src[lane i-1], lane 0 gets `edge` (wave_shr:1); lane i <- src[lane i+1], lane 63 gets `edge` (wave_shl:1)
-__device__ __forceinline__ float sd_from_below(float edge, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge),
-                                                                 __builtin_bit_cast(int, src), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sd_from_above(float edge, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge),
-                                                                 __builtin_bit_cast(int, src), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sd_lane(float v, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-// a wave's own LDS traffic in program order, for the compiler as well (lanes read what other lanes of the wave wrote)
-__device__ __forceinline__ void sd_wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // utterance b's lengths within the block; false: no alignment (a length below 1, or the corner outside the band)
 __device__ __forceinline__ bool sd_lengths(const SoftDtwParams &p, int b, int &n, int &m) {
@@ -80,15 +65,6 @@ __device__ __forceinline__ void sd_row_span(int i, int n, int m, int band, int &
     jlo = i - band > 0 ? i - band : 0;
     jhi = i + band < m - 1 ? i + band : m - 1;
     if (i >= n) { jlo = 1; jhi = 0; }
-}
-
-// the three softmin weights 2^(mn - x), mn the smallest operand (so one of them is 1 and the sum is in [1, 3])
-__device__ __forceinline__ float sd_weights(float a, float b, float c, float &wa, float &wb, float &wc) {
-    const float mn = fminf(fminf(a, b), c);
-    wa = __builtin_amdgcn_exp2f(mn - a);
-    wb = __builtin_amdgcn_exp2f(mn - b);
-    wc = __builtin_amdgcn_exp2f(mn - c);
-    return mn;
 }
 
 __global__ __launch_bounds__(SD_MAX_N) void softdtw_forward_kernel(SoftDtwParams p) {
@@ -129,7 +105,7 @@ __global__ __launch_bounds__(SD_MAX_N) void softdtw_forward_kernel(SoftDtwParams
                 const int row = row0 + SD_RS * k, col = (t + 1) * SD_TW + col0 - SD_RS * k;
                 float d = SD_BIG;
                 if (row < n && col >= 0 && col < m) d = cost[off0 + (t + 1) * SD_TW + k * kstride];
-                v[k] = fminf(fmaxf(d * p.scale, -SD_BIG), SD_BIG);
+                v[k] = sd_cost_in(d, p.scale);
             }
         }
         if (active && t >= 0 && t < ntl) {
@@ -146,10 +122,7 @@ __global__ __launch_bounds__(SD_MAX_N) void softdtw_forward_kernel(SoftDtwParams
                 const int j = t * SD_TW + c - lane;
                 const float d = dv[c];
                 const float up = sd_from_below(sd_lane(bv, c), prev);
-                float wa, wb, wc;
-                const float mn = sd_weights(upprev, up + p.pen, prev + p.pen, wa, wb, wc);
-                float cur = d + (mn - __builtin_amdgcn_logf((wa + wb) + wc));
-                cur = __builtin_amdgcn_fmed3f(cur, -SD_BIG, SD_BIG);
+                float cur = sd_cell(upprev, up, prev, p.pen, d);
                 const bool valid = j >= jlo && j <= jhi;
                 cur = valid ? cur : SD_BIG;
                 if (R) tile[lane * SD_PITCH + c] = cur;
@@ -243,15 +216,11 @@ __global__ __launch_bounds__(SD_MAX_N) void softdtw_backward_kernel(SoftDtwParam
                     const int j = t * SD_TW + c - lane;
                     const float r2 = r2v[cc];                                             // R[i,j-2]
                     const float x = sd_from_below(sd_lane(above, c), r2);                 // R[i-1,j-1]
-                    float wa, wb, wc;
-                    sd_weights(x, xprev + p.pen, rm1 + p.pen, wa, wb, wc);
-                    const float inv = __builtin_amdgcn_rcpf((wa + wb) + wc);
                     float e = cl + sd_from_above(sd_lane(rv, c), send);
                     if (j == m - 1 && i == n - 1) e = 1.f;
                     e = (j >= jlo && j <= jhi) ? e : 0.f;
-                    const float q = e * inv;
-                    const float cd = q * wa, cu = q * wb;
-                    cl = q * wc;
+                    float cd, cu;
+                    sd_push(x, xprev, rm1, p.pen, e, cd, cu, cl);
                     send = cu + cdprev;                                                   // both land on (i-1,j)
                     cdprev = cd;
                     tile[(lane + 1) * SD_PITCH + c] = e;

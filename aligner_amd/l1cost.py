@@ -13,31 +13,18 @@ soft_dtw's cells exist and without the cdist graph.  Channels come first: pred [
 """
 from __future__ import annotations
 
-import math
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib
-from ._operands import f32c, lengths, one_gpu, ptr, stream
+from ._operands import check_reduction, f32c, lengths, one_gpu, pred_target_shapes, ptr, reduced, stream
 from .softdtw import soft_dtw
 
 
 def _checked(pred, target, bandwidth, scale, also=()) -> Tuple[int, int, int, int, int, float, torch.device]:
     """(B, C, N, M, the band as the C ABI takes it, scale, device).  also: (tensor, name) of a further [B,N,M] operand."""
-    for t, name in ((pred, "pred"), (target, "target")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3:
-            raise ValueError(f"{name} must be a [B,C,T] tensor")
-        if not t.is_floating_point():
-            raise ValueError(f"{name} must be a floating-point tensor")
-    B, C, N = pred.shape
-    if target.shape[0] != B or target.shape[1] != C:
-        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} disagree in B or C")
-    if C < 1:
-        raise ValueError("C must be at least 1")
-    scale = float(scale)
-    if not math.isfinite(scale):
-        raise ValueError("scale must be finite")
+    B, C, N, _, scale = pred_target_shapes(pred, target, scale)
     if bandwidth is not None and int(bandwidth) < 0:
         raise ValueError("bandwidth must be None (no band) or at least 0")
     for t, name in also:
@@ -142,13 +129,5 @@ def soft_dtw_l1_loss(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch
     after the forward pass and no cdist graph is kept: what is saved is pred, target, E and the lengths.  Gradients come
     back in the inputs' dtypes, None for an input that does not require one.  reduction and zero_infinity as in
     soft_dtw_loss(); soft_dtw()'s domain (N <= 1024).  Parallel Tacotron 2: gamma 0.05, warp_penalty 128, bandwidth 60."""
-    if reduction not in ("mean", "sum", "none"):
-        raise ValueError("reduction must be 'mean', 'sum' or 'none'")
-    value = _SoftDtwL1Loss.apply(pred, target, n, m, gamma, warp_penalty, bandwidth, scale)
-    if zero_infinity:
-        value = torch.where(torch.isinf(value), torch.zeros_like(value), value)
-    if reduction == "mean":
-        return value.mean()
-    if reduction == "sum":
-        return value.sum()
-    return value
+    check_reduction(reduction)
+    return reduced(_SoftDtwL1Loss.apply(pred, target, n, m, gamma, warp_penalty, bandwidth, scale), reduction, zero_infinity)

@@ -15,13 +15,12 @@ two as one autograd function.  Any other cost is the caller's to build.
 """
 from __future__ import annotations
 
-import math
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib
-from ._operands import f32c, lengths, ptr, stream
+from ._operands import check_reduction, dp_parameters, f32c, lengths, ptr, reduced, stream
 
 _workspaces = _lib.StreamWorkspaces(zero=False)
 
@@ -31,11 +30,7 @@ def _checked(cost, gamma, warp_penalty, bandwidth) -> Tuple[float, float, int]:
         raise ValueError("cost must be a [B,N,M] tensor")
     if not cost.is_floating_point():
         raise ValueError("cost must be a floating-point tensor")
-    gamma, warp_penalty = float(gamma), float(warp_penalty)
-    if not (gamma > 0.0 and math.isfinite(gamma)):
-        raise ValueError("gamma must be positive and finite")
-    if not (warp_penalty >= 0.0 and math.isfinite(warp_penalty)):
-        raise ValueError("warp_penalty must be finite and not negative")
+    gamma, warp_penalty = dp_parameters(gamma, warp_penalty)
     if bandwidth is not None and int(bandwidth) < 0:
         raise ValueError("bandwidth must be None (no band) or at least 0")
     if not cost.is_cuda:
@@ -99,13 +94,5 @@ def soft_dtw_loss(cost: torch.Tensor, n: Optional[torch.Tensor] = None, m: Optio
     warp_penalty 128 and bandwidth 60 on the summed L1 cost.  reduction: "mean" (a plain mean over the batch), "sum"
     or "none".  zero_infinity: an utterance without an alignment (value +inf) contributes 0 and no gradient instead of
     making the batch loss +inf.  No gradient for gamma or the penalty."""
-    if reduction not in ("mean", "sum", "none"):
-        raise ValueError("reduction must be 'mean', 'sum' or 'none'")
-    value = _SoftDtwLoss.apply(cost, n, m, gamma, warp_penalty, bandwidth)
-    if zero_infinity:
-        value = torch.where(torch.isinf(value), torch.zeros_like(value), value)
-    if reduction == "mean":
-        return value.mean()
-    if reduction == "sum":
-        return value.sum()
-    return value
+    check_reduction(reduction)
+    return reduced(_SoftDtwLoss.apply(cost, n, m, gamma, warp_penalty, bandwidth), reduction, zero_infinity)

@@ -47,7 +47,9 @@ extern "C" {
  *    the hard path -- aligner_gauss_nll_f32 / aligner_gauss_nll_workspace_bytes; and Gaussian upsampling with its
  *    gradient -- aligner_gauss_upsample_f32 / aligner_gauss_upsample_backward_f32 and their *_workspace_bytes; and
  *    Soft-DTW with its expected alignment matrix -- aligner_soft_dtw_f32 / aligner_soft_dtw_workspace_bytes; and its
- *    banded L1 cost table with the gradient -- aligner_l1_cost_f32 / aligner_l1_cost_backward_f32. */
+ *    banded L1 cost table with the gradient -- aligner_l1_cost_f32 / aligner_l1_cost_backward_f32; the three in band
+ *    storage, O(N w) memory and any N -- aligner_soft_dtw_banded_f32 / aligner_l1_cost_banded_f32 /
+ *    aligner_l1_cost_banded_backward_f32. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -826,6 +828,42 @@ int aligner_l1_cost_backward_f32(const float *grad_cost_dev, const float *pred_d
                                  const int32_t *n_dev, const int32_t *m_dev, int bandwidth, float scale,
                                  const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
                                  int B, int C, int N, int M, void *hip_stream);
+
+/*
+ * Soft-DTW, its L1 cost and the cost's gradient in band storage: O(N w) memory and no limit on N.  Build-defined.
+ * Band storage of bandwidth w is a contiguous fp32 tensor [B,N,W], W = 2 w + 1, 0 <= w <= 127; element [b,i,d] is
+ * cell (i,j) with j = i + d - w, so |i - j| <= w by construction.  With n = n_dev[b] clamped to [0,N] and m = m_dev[b]
+ * clamped to [0,N+w] (null: N; no larger column can be stored), a cell exists iff i < n and 0 <= j < m.
+ *
+ * R, value and E are those of aligner_soft_dtw_f32 on the dense image with band w: the same recurrence, penalty,
+ * forbidden +inf cells and "no alignment" convention (value +inf and an all-zero E when |n - m| > w, a length is
+ * below 1, or +inf costs cross every path), from the same per-cell arithmetic.  An element whose cell does not exist
+ * is never read as a value, by the DP or by the cost gradient (a NaN there reaches nothing), and every output writes
+ * it as exactly 0, the cost table included (band storage has no "outside the band" to mark with +inf).
+ *   cost_band_dev     [B,N,W] fp32 contiguous; value_out_dev [B] fp32
+ *   grad_band_out_dev optional [B,N,W] fp32: E.  Between the two launches it holds R; E overwrites it in place.
+ *   ws_dev            aligner_soft_dtw_banded_workspace_bytes(B,N,bandwidth,want_grad) bytes (0: outside the domain)
+ * The cost calls take pred [B,C,N] and target [B,C,M] as aligner_l1_cost_f32 does, with m additionally clamped to M
+ * (columns j >= M have no target), the same formulas, sign(0) = 0 and row_scale; either of dpred_out_dev [B,C,N] and
+ * dtarget_out_dev [B,C,M] may be null, not both, and each has the same bits whether or not the other is asked for.
+ * One workgroup per utterance in the DP (one wave walks the anti-diagonals of the band), one owner per output element
+ * and a fixed order of summation in the cost calls, no atomics: the same bits on every call.  Domain:
+ * 0 <= bandwidth <= 127, B <= 65535, C <= 4096, N*W < 2^29, no other limit on N or M: ALIGNER_EDOM beyond (a negative
+ * bandwidth: ALIGNER_EINVAL); ALIGNER_EINVAL and ALIGNER_ENOSPC as in the dense calls.  Validated before any HIP call.
+ * No allocation and no synchronisation inside; asynchronous on the stream, capturable.
+ */
+size_t aligner_soft_dtw_banded_workspace_bytes(int B, int N, int bandwidth, int want_grad);
+int aligner_soft_dtw_banded_f32(const float *cost_band_dev, const int32_t *n_dev, const int32_t *m_dev,
+                                float gamma, float warp_penalty, int bandwidth,
+                                float *value_out_dev, float *grad_band_out_dev,
+                                void *ws_dev, size_t ws_bytes, int B, int N, void *hip_stream);
+int aligner_l1_cost_banded_f32(const float *pred_dev, const float *target_dev, const int32_t *n_dev, const int32_t *m_dev,
+                               int bandwidth, float scale, float *cost_band_out_dev,
+                               int B, int C, int N, int M, void *hip_stream);
+int aligner_l1_cost_banded_backward_f32(const float *grad_band_dev, const float *pred_dev, const float *target_dev,
+                                        const int32_t *n_dev, const int32_t *m_dev, int bandwidth, float scale,
+                                        const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
+                                        int B, int C, int N, int M, void *hip_stream);
 
 #ifdef __cplusplus
 }
