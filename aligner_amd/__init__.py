@@ -26,6 +26,7 @@ from .softdtw import soft_dtw, soft_dtw_loss  # noqa: F401
 from .l1cost import l1_cost, l1_cost_backward, soft_dtw_l1_loss  # noqa: F401
 from .banddtw import (band_to_dense, dense_to_band, l1_cost_banded, l1_cost_banded_backward, soft_dtw_banded,  # noqa: F401
                       soft_dtw_banded_loss, soft_dtw_l1_banded_loss)
+from .dtwpath import DtwPath, dtw_path, dtw_path_banded, dtw_path_l1, path_to_dense  # noqa: F401
 
 __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status",
            "soft_attention", "soft_attention_backward", "conv1d", "conv1d_backward", "alignment_encoder", "AlignmentEncoderParams",
@@ -37,6 +38,7 @@ __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status"
            "l1_cost", "l1_cost_backward", "soft_dtw_l1_loss",
            "dense_to_band", "band_to_dense", "soft_dtw_banded", "soft_dtw_banded_loss", "l1_cost_banded",
            "l1_cost_banded_backward", "soft_dtw_l1_banded_loss",
+           "dtw_path", "dtw_path_banded", "dtw_path_l1", "path_to_dense", "DtwPath",
            "install_dropin"]
 
 

@@ -69,14 +69,20 @@ def one_gpu(named, names: str) -> torch.device:
     return dev
 
 
-def dp_parameters(gamma, warp_penalty) -> Tuple[float, float]:
-    """Soft-DTW's (gamma, warp_penalty) as floats, checked."""
-    gamma, warp_penalty = float(gamma), float(warp_penalty)
-    if not (gamma > 0.0 and math.isfinite(gamma)):
-        raise ValueError("gamma must be positive and finite")
+def penalty(warp_penalty) -> float:
+    """The warp penalty of the DTW calls as a float, checked."""
+    warp_penalty = float(warp_penalty)
     if not (warp_penalty >= 0.0 and math.isfinite(warp_penalty)):
         raise ValueError("warp_penalty must be finite and not negative")
-    return gamma, warp_penalty
+    return warp_penalty
+
+
+def dp_parameters(gamma, warp_penalty) -> Tuple[float, float]:
+    """Soft-DTW's (gamma, warp_penalty) as floats, checked."""
+    gamma = float(gamma)
+    if not (gamma > 0.0 and math.isfinite(gamma)):
+        raise ValueError("gamma must be positive and finite")
+    return gamma, penalty(warp_penalty)
 
 
 def pred_target_shapes(pred, target, scale) -> Tuple[int, int, int, int, float]:

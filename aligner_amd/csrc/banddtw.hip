@@ -30,11 +30,10 @@
 #include "common.h"
 #include "device.h"
 #include "softdtw_cell.h"
+#include "dtw_schedule.h"
 
 namespace aligner {
 
-constexpr int BD_T = 32;                    // steps per tile
-constexpr int BD_MAX_W = 127;
 constexpr int BD_BWD_WAVES = 4;             // backward: wave 0 sweeps, the others write zeros
 constexpr int BD_MAX_C = 4096;
 constexpr int BC_RB = 16;                   // rows per wave tile of the cost kernel
@@ -52,55 +51,6 @@ struct BandDtwParams {
     float *grad;            // [B,N,W]: R (scaled) after forward, E after backward; null: value only
     float *fin;             // workspace [B]
     int B, N;
-};
-
-__device__ __forceinline__ bool bd_lengths(const BandDtwParams &p, int b, int &n, int &m) {
-    n = p.ns ? p.ns[b] : p.N;
-    m = p.ms ? p.ms[b] : p.N;
-    n = n < p.N ? n : p.N;
-    m = m < p.N + p.w ? m : p.N + p.w;
-    if (n < 1 || m < 1) return false;
-    const int d = n > m ? n - m : m - n;
-    return d <= p.w;
-}
-
-// A lane's view of one of its cells (column c, slot q): the rows [ia, ia + len) on which the cell exists
-struct BdSlot { int ia; unsigned len; };
-__device__ __forceinline__ BdSlot bd_slot(int c, int q, int w, int wp, int n, int m) {
-    const int d = 2 * c + q - (wp - w);
-    const int e = wp - 2 * c - q;                             // i - j
-    int ia = e > 0 ? e : 0;                                   // j >= 0
-    int ib = m + e < n ? m + e : n;                           // j < m
-    if (d < 0 || d > 2 * w || ib < ia) ib = ia;
-    BdSlot s;
-    s.ia = ia;
-    s.len = (unsigned)(ib - ia);
-    return s;
-}
-
-// The movers' element k of tile s0: row rtop + 2 k + (lane >> 5), step t = lane & 31; column c, band index d.
-// NC columns and BD_T steps: every (t, c) of the tile belongs to exactly one (k, lane).
-template <int NC> struct BdMover {
-    static constexpr int NK = (NC + BD_T / 2) / 2;
-    int row0, c0, d0, t;
-    __device__ __forceinline__ BdMover(int s0, int w, int wp, int lane) {
-        const int hb = (s0 + wp) >> 1;                        // (s0 + wp is even; arithmetic shift for tile -1)
-        t = lane & 31;
-        row0 = hb - (NC - 1) + (lane >> 5);
-        c0 = hb - row0 + (t >> 1);
-        d0 = 2 * c0 + (t & 1) - (wp - w);
-    }
-    __device__ __forceinline__ int row(int k) const { return row0 + 2 * k; }
-    __device__ __forceinline__ int col(int k) const { return c0 - 2 * k; }
-    __device__ __forceinline__ int d(int k) const { return d0 - 4 * k; }
-    // element k is a cell that exists (then its column is in [0, NC) as well); off: its place in the utterance's block
-    __device__ __forceinline__ bool cell(int k, int n, int m, int w, int &off) const {
-        const int r = row(k), dk = d(k), j = r + dk - w;
-        off = r * (2 * w + 1) + dk;
-        return r >= 0 && r < n && dk >= 0 && dk <= 2 * w && j >= 0 && j < m;
-    }
-    __device__ __forceinline__ bool staged(int k) const { return col(k) >= 0 && col(k) < NC; }
-    __device__ __forceinline__ int lds(int k, int pitch) const { return t * pitch + col(k); }
 };
 
 template <int NC>

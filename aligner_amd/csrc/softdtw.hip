@@ -25,16 +25,9 @@
 #include "common.h"
 #include "device.h"
 #include "softdtw_cell.h"
+#include "dtw_schedule.h"
 
 namespace aligner {
-
-constexpr int   SD_TW = 16;                               // steps (and staged floats per row) per tile
-constexpr int   SD_PITCH = SD_TW + 1;                     // odd: a step's 64 lanes read 64 banks
-constexpr int   SD_LAG = (63 + SD_TW - 1) / SD_TW + 1;    // tiles between neighbouring waves
-constexpr int   SD_RS = 64 / SD_TW;                       // rows a wave moves per pass of a tile
-constexpr int   SD_RING = 64;                             // hand-off ring of a wave, entries (a column each)
-constexpr int   SD_MAX_N = 1024;
-constexpr int   SD_NO_BAND = 1 << 30;
 
 struct SoftDtwParams {
     const float *cost;      // [B,N,M]
@@ -48,24 +41,6 @@ struct SoftDtwParams {
     float *fin;             // workspace [B]: R[n-1,m-1] scaled, SD_BIG without an alignment
     int B, N, M;
 };
-
-// utterance b's lengths within the block; false: no alignment (a length below 1, or the corner outside the band)
-__device__ __forceinline__ bool sd_lengths(const SoftDtwParams &p, int b, int &n, int &m) {
-    n = p.ns ? p.ns[b] : p.N;
-    m = p.ms ? p.ms[b] : p.M;
-    n = n < p.N ? n : p.N;
-    m = m < p.M ? m : p.M;
-    if (n < 1 || m < 1) return false;
-    const int d = n > m ? n - m : m - n;
-    return d <= p.band;
-}
-
-// the columns of row i that exist: [jlo, jhi], empty for a row past the utterance
-__device__ __forceinline__ void sd_row_span(int i, int n, int m, int band, int &jlo, int &jhi) {
-    jlo = i - band > 0 ? i - band : 0;
-    jhi = i + band < m - 1 ? i + band : m - 1;
-    if (i >= n) { jlo = 1; jhi = 0; }
-}
 
 __global__ __launch_bounds__(SD_MAX_N) void softdtw_forward_kernel(SoftDtwParams p) {
     extern __shared__ __attribute__((aligned(16))) float sd_smem[];
@@ -246,9 +221,6 @@ __global__ __launch_bounds__(SD_MAX_N) void softdtw_backward_kernel(SoftDtwParam
     }
 }
 
-static bool sd_shape_ok(int B, int N, int M) {
-    return B >= 1 && N >= 1 && M >= 1 && B <= 65535 && N <= SD_MAX_N && (long long)N * M < (1ll << 29);
-}
 static size_t sd_lds_bytes(int NW, bool backward) {
     return (size_t)NW * ((backward ? 65 : 64) * SD_PITCH + SD_RING) * sizeof(float);
 }

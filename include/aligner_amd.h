@@ -49,7 +49,8 @@ extern "C" {
  *    Soft-DTW with its expected alignment matrix -- aligner_soft_dtw_f32 / aligner_soft_dtw_workspace_bytes; and its
  *    banded L1 cost table with the gradient -- aligner_l1_cost_f32 / aligner_l1_cost_backward_f32; the three in band
  *    storage, O(N w) memory and any N -- aligner_soft_dtw_banded_f32 / aligner_l1_cost_banded_f32 /
- *    aligner_l1_cost_banded_backward_f32. */
+ *    aligner_l1_cost_banded_backward_f32; and hard DTW, the minimum-cost warping path with its backtrack, in both
+ *    storage forms -- aligner_dtw_path_f32 / aligner_dtw_path_banded_f32 and their *_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -864,6 +865,53 @@ int aligner_l1_cost_banded_backward_f32(const float *grad_band_dev, const float 
                                         const int32_t *n_dev, const int32_t *m_dev, int bandwidth, float scale,
                                         const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
                                         int B, int C, int N, int M, void *hip_stream);
+
+/*
+ * Hard DTW: the minimum-cost warping path between two frame sequences, with its backtrack -- the hard counterpart of
+ * aligner_soft_dtw_f32 / aligner_soft_dtw_banded_f32 (the gamma -> 0 limit, which those calls cannot take), and what an
+ * MCD-DTW or L1-along-the-path evaluation needs.  Build-defined.  For utterance b take n = n_dev[b], m = m_dev[b],
+ * clamped as the soft calls clamp them, a warp penalty p (finite, >= 0) and a band w.  Cell (i,j) exists iff i < n,
+ * j < m and |i - j| <= w.  All in fp32, in exactly this order:
+ *
+ *     a = R[i-1,j-1]                 (R[-1,-1] = 0; every other border cell +inf)
+ *     b = R[i-1,j] + p
+ *     c = R[i,j-1] + p
+ *     best = a, k = 0;  if (b < best) { best = b; k = 1 }   if (c < best) { best = c; k = 2 }
+ *     d = cost[i,j]
+ *     R[i,j] = +inf            if the cell does not exist, or d is +inf or NaN, or best is +inf
+ *            = best + d        otherwise
+ *     value = R[n-1,m-1]
+ *
+ * Both comparisons are strict: a tie prefers the diagonal, then the move that advances the row, then the move that
+ * advances the column.  A -inf cost is legal and propagates; nothing computes inf - inf.  The path starts at
+ * (n-1,m-1), follows k until (0,0) and is reported in ascending order; its length K satisfies
+ * max(n,m) <= K <= n+m-1.  An utterance without an alignment (a length below 1, |n - m| > w, a +inf value) has
+ * value +inf, length 0 and a path of all -1.  No scaling and no sentinel: two additions and two comparisons per cell,
+ * so value, path and length are functions of the costs' bits, the same in both storage forms.
+ *   cost_dev       [B,N,M] fp32 contiguous (dense), or cost_band_dev [B,N,W] in band storage (above; m null: N)
+ *   value_out_dev  [B] fp32
+ *   path_out_dev   optional [B,L,2] int32, L = N+M-1 (dense) or 2N+w-1 (band storage): the K pairs (i,j), then -1
+ *   length_out_dev [B] int32: K; null iff path_out_dev is
+ *   ws_dev         aligner_dtw_path_workspace_bytes(B,N,M) / aligner_dtw_path_banded_workspace_bytes(B,N,bandwidth)
+ *                  bytes (0: outside the domain): the decisions k, a byte a cell.  Needed (and written) only with a path;
+ *                  without one only the forward kernel runs, and ws_dev may be null.
+ * One workgroup per utterance in each launch (forward, then the backtrack: one wave follows the decisions through
+ * windows of 64 rows staged in LDS), no atomics: the same bits on every call.  Domain: that of the soft call of the
+ * same storage form (dense: N <= 1024, B <= 65535, N*M < 2^29; band storage: 0 <= bandwidth <= 127, B <= 65535,
+ * N*W < 2^29): ALIGNER_EDOM beyond; ALIGNER_EINVAL for a null pointer, a shape below 1, a penalty that is negative or
+ * not finite, a bandwidth below -1 (band storage: below 0); ALIGNER_ENOSPC for a workspace that is too small.
+ * Validated before any HIP call.  Asynchronous on the stream, capturable.
+ */
+size_t aligner_dtw_path_workspace_bytes(int B, int N, int M);
+int aligner_dtw_path_f32(const float *cost_dev, const int32_t *n_dev, const int32_t *m_dev,
+                         float warp_penalty, int bandwidth,
+                         float *value_out_dev, int32_t *path_out_dev, int32_t *length_out_dev,
+                         void *ws_dev, size_t ws_bytes, int B, int N, int M, void *hip_stream);
+size_t aligner_dtw_path_banded_workspace_bytes(int B, int N, int bandwidth);
+int aligner_dtw_path_banded_f32(const float *cost_band_dev, const int32_t *n_dev, const int32_t *m_dev,
+                                float warp_penalty, int bandwidth,
+                                float *value_out_dev, int32_t *path_out_dev, int32_t *length_out_dev,
+                                void *ws_dev, size_t ws_bytes, int B, int N, void *hip_stream);
 
 #ifdef __cplusplus
 }
