@@ -2,22 +2,8 @@
 // W = 2w + 1, element [i,d] is cell (i, j = i + d - w).  Memory is O(N w) and N has no limit of its own; the cell
 // arithmetic is softdtw_cell.h's, shared with the dense kernels.
 //
-// The DP.  One workgroup per utterance, and one wave of it walks the anti-diagonals s = i + j, one a step.  With
-// o = w & 1 and dd = d + o, a cell sits in column c = dd >> 1 (0 .. w) and slot q = dd & 1 of the band, and on
-// anti-diagonal s exactly the cells with q = s & 1 are present: one per column.  Lane l owns column l, and for
-// w > 63 column 64 + l as well -- two independent cells a step in one wave, which fill each other's latencies,
-// where two waves would need a hand-off and a barrier a step.  The predecessors of (c,q) are (c,q) itself two steps
-// back, and one step back (c,1) and (c-1,1) for q = 0, (c,0) and (c+1,0) for q = 1: the lane's own registers and
-// one DPP move from a neighbour lane (column 63 <-> 64: a readlane into the move's edge value).  No LDS, no barrier
-// and no other wave on the dependent chain.
-//
-// Staging.  A tile is BD_T = 32 steps.  In memory the cells of a tile are, for each row i, the BD_T consecutive
-// floats d = s0 + w - 2 i + t (t = 0 .. 31): 128-byte segments, two rows per wave load, issued for the next tile
-// before the current tile's steps.  In LDS the tile is [t][column] at a pitch of PITCH = NC + 16 floats
-// (NC = 64 or 128 columns), so a step reads lane-linear addresses.  The movers' store has lane t of a row at
-// t PITCH + c0 + (t >> 1); PITCH = 16 (mod 32), so even t = 2k fall on bank c0 + k and odd t = 2k + 1 on bank
-// c0 + k + 16: the 32 lanes of a row (an LDS store is served 32 lanes at a time, on 32 banks) hit 32 banks.
-// R leaves the forward kernel through the same tile.
+// Forward is dtw_forward.h's band-storage kernel with the soft cell; the walk along the anti-diagonals, the columns and
+// slots of a lane and the staging of a tile are described there.
 //
 // Backward never reads the costs: it sweeps the tiles in reverse over the stored R (two tiles resident in an LDS
 // ring, since a cell needs R one and two steps back, columns c - 1 .. c + 1 read straight from LDS, off the chain),
@@ -31,6 +17,7 @@
 #include "device.h"
 #include "softdtw_cell.h"
 #include "dtw_schedule.h"
+#include "dtw_forward.h"
 
 namespace aligner {
 
@@ -42,125 +29,8 @@ constexpr int BC_TR = 8;                    // rows per step (dtarget)
 constexpr int BC_PR = 8;                    // rows per wave (dpred): BC_PR * BC_CC == 64 sums
 constexpr int BC_PITCH = 65;
 
-struct BandDtwParams {
-    const float *cost;      // [B,N,W]
-    const int   *ns, *ms;   // [B] or null
-    float scale, pen, unscale;
-    int   w;
-    float *value;           // [B]
-    float *grad;            // [B,N,W]: R (scaled) after forward, E after backward; null: value only
-    float *fin;             // workspace [B]
-    int B, N;
-};
-
 template <int NC>
-__global__ __launch_bounds__(64) void banddtw_forward_kernel(BandDtwParams p) {
-    constexpr int PITCH = NC + 16, NP = NC / 64, NK = BdMover<NC>::NK;
-    __shared__ float tile[BD_T * PITCH];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    int n, m;
-    if (!bd_lengths(p, b, n, m)) {
-        if (lane == 0) { p.value[b] = __builtin_huge_valf(); p.fin[b] = SD_BIG; }
-        return;
-    }
-    const int w = p.w, W = 2 * w + 1, wp = w + (w & 1);
-    const size_t ubase = (size_t)b * p.N * W;
-    const float *cost = p.cost + ubase;
-    float *R = p.grad ? p.grad + ubase : nullptr;
-    const int slast = n + m - 2, ntl = slast / BD_T + 1;
-    BdSlot sl[NP][2];
-    float x[NP][2];                                           // the lane's cells as of their last step
-#pragma unroll
-    for (int a = 0; a < NP; ++a)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            sl[a][q] = bd_slot(64 * a + lane, q, w, wp, n, m);
-            x[a][q] = (q == 0 && 2 * (64 * a + lane) == wp) ? 0.f : SD_BIG;      // R[-1,-1] = 0, two steps before (0,0)
-        }
-    float v[NK];
-    auto load = [&](int tl) {
-        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            int off;
-            float c = SD_BIG;
-            if (mv.cell(k, n, m, w, off)) c = cost[off];
-            v[k] = sd_cost_in(c, p.scale);
-        }
-    };
-    auto stage = [&](int tl) {
-        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            if (mv.staged(k)) tile[mv.lds(k, PITCH)] = v[k];
-        }
-    };
-    load(0);
-    stage(0);
-    sd_wave_lds_sync();
-    for (int tl = 0; tl < ntl; ++tl) {
-        if (tl + 1 < ntl) load(tl + 1);
-        const int hb = (tl * BD_T + wp) >> 1;
-        int rel[NP][2];                                       // row of the slot's cell at t = 0 or 1, from ia
-#pragma unroll
-        for (int a = 0; a < NP; ++a)
-#pragma unroll
-            for (int q = 0; q < 2; ++q) rel[a][q] = hb - (64 * a + lane) - sl[a][q].ia;
-#pragma unroll 1
-        for (int t8 = 0; t8 < BD_T; t8 += 8) {
-            float dv[8][NP];
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt)
-#pragma unroll
-                for (int a = 0; a < NP; ++a) dv[tt][a] = tile[(t8 + tt) * PITCH + 64 * a + lane];
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) {
-                const int q = tt & 1, u = (t8 + tt) >> 1;
-                float nb[NP];                                 // the neighbour column's cell of the step before
-                if (q == 0) {                                 // (c-1, 1)
-                    nb[0] = sd_from_below(SD_BIG, x[0][1]);
-                    if (NP == 2) nb[NP - 1] = sd_from_below(sd_lane(x[0][1], 63), x[NP - 1][1]);
-                } else {                                      // (c+1, 0)
-                    nb[NP - 1] = sd_from_above(SD_BIG, x[NP - 1][0]);
-                    if (NP == 2) nb[0] = sd_from_above(sd_lane(x[NP - 1][0], 0), x[0][0]);
-                }
-#pragma unroll
-                for (int a = 0; a < NP; ++a) {
-                    const float up = q == 0 ? x[a][1] : nb[a], left = q == 0 ? nb[a] : x[a][0];
-                    float cur = sd_cell(x[a][q], up, left, p.pen, dv[tt][a]);
-                    cur = (unsigned)(rel[a][q] + u) < sl[a][q].len ? cur : SD_BIG;
-                    x[a][q] = cur;
-                    tile[(t8 + tt) * PITCH + 64 * a + lane] = cur;
-                }
-            }
-        }
-        sd_wave_lds_sync();
-        if (tl == ntl - 1) {                                  // cell (n-1, m-1): step slast, e = n - m
-            const int dd = wp - (n - m);
-            const float fin = tile[(slast - tl * BD_T) * PITCH + (dd >> 1)];
-            if (lane == 0) {
-                p.fin[b] = fin;
-                p.value[b] = fin < 0.5f * SD_BIG ? fin * p.unscale : __builtin_huge_valf();
-            }
-        }
-        if (R) {
-            const BdMover<NC> mv(tl * BD_T, w, wp, lane);
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                int off;
-                if (mv.cell(k, n, m, w, off)) R[off] = tile[mv.lds(k, PITCH)];
-            }
-            sd_wave_lds_sync();
-        }
-        if (tl + 1 < ntl) {
-            stage(tl + 1);
-            sd_wave_lds_sync();
-        }
-    }
-}
-
-template <int NC>
-__global__ __launch_bounds__(64 * BD_BWD_WAVES) void banddtw_backward_kernel(BandDtwParams p) {
+__global__ __launch_bounds__(64 * BD_BWD_WAVES) void banddtw_backward_kernel(DtwParams p) {
     constexpr int PITCH = NC + 16, NP = NC / 64, NK = BdMover<NC>::NK;
     static_assert(NC + 2 <= PITCH, "columns -1 and NC");
     __shared__ float ring[2 * BD_T * PITCH];                  // [step & 63][column + 1]
@@ -441,21 +311,13 @@ __global__ __launch_bounds__(64) void band_l1_dpred_kernel(
     if (stored) *out = oi < n ? sum * k : 0.f;
 }
 
-static int bd_domain(int B, int N, int bandwidth) {
-    if (bandwidth > BD_MAX_W) return fail(ALIGNER_EDOM, "bandwidth=%d too large (<= %d; the dense calls take any band)", bandwidth, BD_MAX_W);
-    if (B > 65535) return fail(ALIGNER_EDOM, "B=%d too large", B);
-    if ((long long)N * (2 * bandwidth + 1) >= (1ll << 29))
-        return fail(ALIGNER_EDOM, "N*W=%lld too large (< 2^29)", (long long)N * (2 * bandwidth + 1));
-    return ALIGNER_OK;
-}
-
 static int bc_check(int B, int C, int N, int M, float scale, int bandwidth) {
     if (B < 1 || C < 1 || N < 1 || M < 1) return fail(ALIGNER_EINVAL, "bad shape");
     if (!(scale == scale) || !(scale < __builtin_huge_valf()) || !(scale > -__builtin_huge_valf()))
         return fail(ALIGNER_EINVAL, "scale must be finite");
     if (bandwidth < 0) return fail(ALIGNER_EINVAL, "bandwidth must be at least 0");
     if (C > BD_MAX_C) return fail(ALIGNER_EDOM, "C=%d too large (<= %d)", C, BD_MAX_C);
-    return bd_domain(B, N, bandwidth);
+    return dtw_band_domain(B, N, bandwidth);
 }
 
 }  // namespace aligner
@@ -466,8 +328,7 @@ extern "C" {
 
 size_t aligner_soft_dtw_banded_workspace_bytes(int B, int N, int bandwidth, int want_grad) {
     (void)want_grad;                                          // R lives in the gradient buffer: one float per utterance either way
-    if (B < 1 || N < 1 || bandwidth < 0 || bandwidth > BD_MAX_W || B > 65535) return 0;
-    if ((long long)N * (2 * bandwidth + 1) >= (1ll << 29)) return 0;
+    if (!bd_shape_ok(B, N, bandwidth)) return 0;
     return align_up((size_t)B * sizeof(float), 256);
 }
 
@@ -477,26 +338,21 @@ int aligner_soft_dtw_banded_f32(const float *cost_band, const int32_t *n_dev, co
     if (!cost_band || !value_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
     if (B < 1 || N < 1) return fail(ALIGNER_EINVAL, "bad shape");
     if (!(gamma > 0.f) || !(gamma < __builtin_huge_valf())) return fail(ALIGNER_EINVAL, "gamma must be positive and finite");
-    if (!(warp_penalty >= 0.f) || !(warp_penalty < __builtin_huge_valf()))
-        return fail(ALIGNER_EINVAL, "warp_penalty must be finite and not negative");
+    if (const int rc = dtw_check_penalty(warp_penalty)) return rc;
     if (bandwidth < 0) return fail(ALIGNER_EINVAL, "bandwidth must be at least 0");
-    if (const int rc = bd_domain(B, N, bandwidth)) return rc;
+    if (const int rc = dtw_band_domain(B, N, bandwidth)) return rc;
     const size_t need = aligner_soft_dtw_banded_workspace_bytes(B, N, bandwidth, grad_band_out != nullptr);
     if (workspace_bytes < need)
         return fail(ALIGNER_ENOSPC, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    BandDtwParams p;
+    DtwParams p = {};
     p.cost = cost_band; p.ns = n_dev; p.ms = m_dev;
-    const double scale = 1.4426950408889634 / (double)gamma;
-    p.scale = (float)scale;
-    const double pen = (double)warp_penalty * scale;
-    p.pen = pen < (double)SD_BIG ? (float)pen : SD_BIG;
-    p.unscale = (float)((double)gamma * 0.6931471805599453);
-    p.w = bandwidth;
+    dtw_soft_scaling(p, gamma, warp_penalty);
+    p.band = bandwidth; p.w = bandwidth;
     p.value = value_out; p.grad = grad_band_out; p.fin = static_cast<float *>(workspace);
-    p.B = B; p.N = N;
-    if (bandwidth <= 63) hipLaunchKernelGGL(banddtw_forward_kernel<64>, dim3(B), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL(banddtw_forward_kernel<128>, dim3(B), dim3(64), 0, s, p);
+    p.B = B; p.N = N; p.M = N + bandwidth;
+    if (bandwidth <= 63) hipLaunchKernelGGL((dtw_band_forward_kernel<DtwSoft, 64>), dim3(B), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((dtw_band_forward_kernel<DtwSoft, 128>), dim3(B), dim3(64), 0, s, p);
     ALIGNER_HIP_CHECK(hipGetLastError());
     if (grad_band_out) {
         if (bandwidth <= 63) hipLaunchKernelGGL(banddtw_backward_kernel<64>, dim3(B), dim3(64 * BD_BWD_WAVES), 0, s, p);

@@ -8,11 +8,12 @@
 // the costs' bits and the same on every schedule, so the dense and the band kernel agree with each other and with the
 // NumPy float32 restatement of tests/dtwpath_oracle.py bit for bit.
 //
-// Forward, dense: softdtw_forward_kernel's skewed pipeline (a lane per row, a wave per 64 rows, the LDS ring between
-// waves, costs staged in the skewed order).  Forward, band storage: banddtw_forward_kernel's walk (one wave, a lane per
-// band column or two, neighbours by DPP).  Instead of R both write the decision k of every cell that exists, one byte
-// a cell, through the LDS tile the costs came in by, so the stores stay row segments; without a path nothing but the
-// value is written.  The value leaves from the register of the lane that owns (n-1, m-1).
+// Forward: the two kernels of dtw_forward.h -- dense, the skewed pipeline (a lane per row, a wave per 64 rows, the LDS
+// ring between waves, costs staged in the skewed order); band storage, the walk along the anti-diagonals (one wave, a
+// lane per band column or two, neighbours by DPP) -- with the hard cell DtwHard below.  Instead of R both write the
+// decision k of every cell that exists, one byte a cell, through the LDS tile the costs came in by, so the stores stay
+// row segments; without a path nothing but the value is written.  The value leaves from the register of the lane that
+// owns (n-1, m-1).
 //
 // Backtrack: one wave per utterance.  It stages the 64 rows that end at the current cell -- their 64 columns that end
 // there (dense), or all W band elements (band storage, contiguous in memory) -- into LDS; a path cannot leave such a
@@ -25,6 +26,7 @@
 #include "device.h"
 #include "softdtw_cell.h"
 #include "dtw_schedule.h"
+#include "dtw_forward.h"
 
 namespace aligner {
 
@@ -35,222 +37,27 @@ static_assert(64 * DP_BATCH * 4 >= DP_WIN * 127 + 3 && 2 * 64 * DP_BATCH * 4 >= 
               "a band window fits one batch of words a lane at w <= 63, two beyond");
 constexpr int DP_SHIFT = 4;                 // chunks of 64 pairs the move to the front has in flight
 
-struct DtwPathParams {
-    const float *cost;      // [B,N,M] or [B,N,W]
-    const int   *ns, *ms;   // [B] or null
-    float pen;
-    int   band;             // dense: SD_NO_BAND for none
-    int   w;                // band storage
-    float *value;           // [B]
-    unsigned char *dec;     // [B,N,M] or [B,N,W] decisions; null: value only
-    int   *path;            // [B,L,2]
-    int   *length;          // [B]
-    int B, N, M, L;         // L = N + M - 1 or 2 N + w - 1
+// The hard cell for dtw_forward.h: true infinities, costs unchanged; a cell keeps the move it came by (0: diagonal,
+// 1: from the row above, 2: from the column before), a byte in the table, and the value alone leaves the kernel
+struct DtwHard {
+    using Out = unsigned char;
+    static constexpr bool TILE_HOLDS_VALUE = false;
+    static __device__ __forceinline__ float none() { return __builtin_huge_valf(); }
+    static __device__ __forceinline__ float in(const DtwParams &, float d) { return d; }
+    static __device__ __forceinline__ float cell(const DtwParams &p, float diag, float up, float left, float d, int &k) {
+        const float inf = __builtin_huge_valf();
+        const float b = up + p.pen, c = left + p.pen;
+        float best = diag;
+        k = 0;
+        if (b < best) { best = b; k = 1; }
+        if (c < best) { best = c; k = 2; }
+        return (d < inf && best < inf) ? best + d : inf;      // (d < inf is false for a NaN as well)
+    }
+    static __device__ __forceinline__ float keep(float, int k) { return __int_as_float(k); }
+    static __device__ __forceinline__ unsigned char *table(const DtwParams &p) { return p.dec; }
+    static __device__ __forceinline__ unsigned char out(float x) { return (unsigned char)__float_as_int(x); }
+    static __device__ __forceinline__ void finish(const DtwParams &p, int b, float fin) { p.value[b] = fin; }
 };
-
-// One cell: the value and, in k, the move it came by (0: diagonal, 1: from the row above, 2: from the column before)
-__device__ __forceinline__ float dp_cell(float diag, float up, float left, float pen, float d, int &k) {
-    const float inf = __builtin_huge_valf();
-    const float b = up + pen, c = left + pen;
-    float best = diag;
-    k = 0;
-    if (b < best) { best = b; k = 1; }
-    if (c < best) { best = c; k = 2; }
-    return (d < inf && best < inf) ? best + d : inf;          // (d < inf is false for a NaN as well)
-}
-
-__global__ __launch_bounds__(SD_MAX_N) void dtwpath_forward_kernel(DtwPathParams p) {
-    extern __shared__ __attribute__((aligned(16))) float dp_smem[];
-    const float inf = __builtin_huge_valf();
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), NW = blockDim.x >> 6;
-    int n, m;
-    if (!sd_lengths(p, b, n, m)) {
-        if (tid == 0) p.value[b] = inf;
-        return;
-    }
-    const int nw = (n + 63) >> 6;                             // waves that own rows of this utterance
-    const bool active = w < nw;
-    float *tile = dp_smem + w * 64 * SD_PITCH;                // [64][SD_PITCH] this wave's costs, then its decisions
-    float *ring = dp_smem + NW * 64 * SD_PITCH;               // [NW][SD_RING] each wave's last row, by column
-    const int ntl = (m + 64 + SD_TW - 1) / SD_TW;
-    const int nph = ntl + SD_LAG * (nw - 1) + 1;
-    const size_t ubase = (size_t)b * p.N * p.M;
-    const float *cost = p.cost + ubase;
-    unsigned char *dec = p.dec ? p.dec + ubase : nullptr;
-    const int i = 64 * w + lane;
-    int jlo, jhi;
-    sd_row_span(i, n, m, p.band, jlo, jhi);
-    // the movers' element k of a tile, as in softdtw_forward_kernel
-    const int r0 = lane / SD_TW, c0 = lane % SD_TW, row0 = 64 * w + r0, col0 = c0 - r0;
-    const int off0 = row0 * p.M + col0, kstride = SD_RS * (p.M - 1), lds0 = r0 * SD_PITCH + c0;
-    float prev = inf;                                         // R[i,j-1]
-    float upprev = i == 0 ? 0.f : inf;                        // R[i-1,j-1]; R[-1,-1] = 0
-    float fin = inf;
-    for (int ph = 0; ph < nph; ++ph) {
-        const int t = ph - SD_LAG * w - 1;
-        const bool ldnext = active && t + 1 >= 0 && t + 1 < ntl;
-        float v[SD_TW];
-        if (ldnext) {
-#pragma unroll
-            for (int k = 0; k < SD_TW; ++k) {
-                const int row = row0 + SD_RS * k, col = (t + 1) * SD_TW + col0 - SD_RS * k;
-                float d = inf;
-                if (row < n && col >= 0 && col < m) d = cost[off0 + (t + 1) * SD_TW + k * kstride];
-                v[k] = d;
-            }
-        }
-        if (active && t >= 0 && t < ntl) {
-            float bv = inf;                                   // the row above this wave's first, columns of this tile
-            if (w > 0 && lane < SD_TW) {
-                const int col = t * SD_TW + lane;
-                if (col < m) bv = ring[(w - 1) * SD_RING + (col & (SD_RING - 1))];
-            }
-            float dv[SD_TW];
-#pragma unroll
-            for (int c = 0; c < SD_TW; ++c) dv[c] = tile[lane * SD_PITCH + c];
-#pragma unroll
-            for (int c = 0; c < SD_TW; ++c) {
-                const int j = t * SD_TW + c - lane;
-                const float up = sd_from_below(sd_lane(bv, c), prev);
-                int k;
-                float cur = dp_cell(upprev, up, prev, p.pen, dv[c], k);
-                const bool valid = j >= jlo && j <= jhi;
-                cur = valid ? cur : inf;
-                if (dec) tile[lane * SD_PITCH + c] = __int_as_float(k);
-                if (lane == 63) ring[w * SD_RING + (j & (SD_RING - 1))] = cur;
-                if (valid && j == m - 1 && i == n - 1) fin = cur;
-                upprev = up;
-                prev = cur;
-            }
-            if (dec) {
-                sd_wave_lds_sync();
-#pragma unroll
-                for (int k = 0; k < SD_TW; ++k) {
-                    const int row = row0 + SD_RS * k, col = t * SD_TW + col0 - SD_RS * k;
-                    if (row < n && col >= 0 && col < m)
-                        dec[off0 + t * SD_TW + k * kstride] = (unsigned char)__float_as_int(tile[lds0 + k * SD_RS * SD_PITCH]);
-                }
-            }
-        }
-        if (ldnext) {
-#pragma unroll
-            for (int k = 0; k < SD_TW; ++k) tile[lds0 + k * SD_RS * SD_PITCH] = v[k];
-        }
-        lds_barrier();
-    }
-    if (i == n - 1) p.value[b] = fin;
-}
-
-template <int NC>
-__global__ __launch_bounds__(64) void dtwpath_band_forward_kernel(DtwPathParams p) {
-    constexpr int PITCH = NC + 16, NP = NC / 64, NK = BdMover<NC>::NK;
-    __shared__ float tile[BD_T * PITCH];
-    const float inf = __builtin_huge_valf();
-    const int b = blockIdx.x, lane = threadIdx.x;
-    int n, m;
-    if (!bd_lengths(p, b, n, m)) {
-        if (lane == 0) p.value[b] = inf;
-        return;
-    }
-    const int w = p.w, W = 2 * w + 1, wp = w + (w & 1);
-    const size_t ubase = (size_t)b * p.N * W;
-    const float *cost = p.cost + ubase;
-    unsigned char *dec = p.dec ? p.dec + ubase : nullptr;
-    const int slast = n + m - 2, ntl = slast / BD_T + 1;
-    const int ddfin = wp - (n - m);                           // cell (n-1, m-1): column ddfin >> 1, slot ddfin & 1
-    BdSlot sl[NP][2];
-    int finrel[NP][2];                                        // the slot's row n - 1 from ia where it is that cell
-    float x[NP][2];                                           // the lane's cells as of their last step
-    bool own = false;
-#pragma unroll
-    for (int a = 0; a < NP; ++a)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            sl[a][q] = bd_slot(64 * a + lane, q, w, wp, n, m);
-            const bool last = 2 * (64 * a + lane) + q == ddfin;
-            finrel[a][q] = last ? n - 1 - sl[a][q].ia : -0x40000000;
-            own = own || last;
-            x[a][q] = (q == 0 && 2 * (64 * a + lane) == wp) ? 0.f : inf;         // R[-1,-1] = 0, two steps before (0,0)
-        }
-    float fin = inf;
-    float v[NK];
-    auto load = [&](int tl) {
-        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            int off;
-            float c = inf;
-            if (mv.cell(k, n, m, w, off)) c = cost[off];
-            v[k] = c;
-        }
-    };
-    auto stage = [&](int tl) {
-        const BdMover<NC> mv(tl * BD_T, w, wp, lane);
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            if (mv.staged(k)) tile[mv.lds(k, PITCH)] = v[k];
-        }
-    };
-    load(0);
-    stage(0);
-    sd_wave_lds_sync();
-    for (int tl = 0; tl < ntl; ++tl) {
-        if (tl + 1 < ntl) load(tl + 1);
-        const int hb = (tl * BD_T + wp) >> 1;
-        int rel[NP][2];                                       // row of the slot's cell at t = 0 or 1, from ia
-#pragma unroll
-        for (int a = 0; a < NP; ++a)
-#pragma unroll
-            for (int q = 0; q < 2; ++q) rel[a][q] = hb - (64 * a + lane) - sl[a][q].ia;
-#pragma unroll 1
-        for (int t8 = 0; t8 < BD_T; t8 += 8) {
-            float dv[8][NP];
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt)
-#pragma unroll
-                for (int a = 0; a < NP; ++a) dv[tt][a] = tile[(t8 + tt) * PITCH + 64 * a + lane];
-#pragma unroll
-            for (int tt = 0; tt < 8; ++tt) {
-                const int q = tt & 1, u = (t8 + tt) >> 1;
-                float nb[NP];                                 // the neighbour column's cell of the step before
-                if (q == 0) {                                 // (c-1, 1)
-                    nb[0] = sd_from_below(inf, x[0][1]);
-                    if (NP == 2) nb[NP - 1] = sd_from_below(sd_lane(x[0][1], 63), x[NP - 1][1]);
-                } else {                                      // (c+1, 0)
-                    nb[NP - 1] = sd_from_above(inf, x[NP - 1][0]);
-                    if (NP == 2) nb[0] = sd_from_above(sd_lane(x[NP - 1][0], 0), x[0][0]);
-                }
-#pragma unroll
-                for (int a = 0; a < NP; ++a) {
-                    const float up = q == 0 ? x[a][1] : nb[a], left = q == 0 ? nb[a] : x[a][0];
-                    int k;
-                    float cur = dp_cell(x[a][q], up, left, p.pen, dv[tt][a], k);
-                    const int r = rel[a][q] + u;
-                    cur = (unsigned)r < sl[a][q].len ? cur : inf;
-                    fin = r == finrel[a][q] ? cur : fin;
-                    x[a][q] = cur;
-                    if (dec) tile[(t8 + tt) * PITCH + 64 * a + lane] = __int_as_float(k);
-                }
-            }
-        }
-        sd_wave_lds_sync();
-        if (dec) {
-            const BdMover<NC> mv(tl * BD_T, w, wp, lane);
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                int off;
-                if (mv.cell(k, n, m, w, off)) dec[off] = (unsigned char)__float_as_int(tile[mv.lds(k, PITCH)]);
-            }
-            sd_wave_lds_sync();
-        }
-        if (tl + 1 < ntl) {
-            stage(tl + 1);
-            sd_wave_lds_sync();
-        }
-    }
-    if (own) p.value[b] = fin;
-}
 
 // The index maps of the backtrack: where a window's decisions are in memory and in LDS.  A window is aimed at the cell
 // it ends at, loaded into registers (every load in flight before the first is waited for: no branch around a load, a
@@ -260,8 +67,8 @@ struct DpDenseMap {
     static constexpr int LDS_BYTES = DP_WIN * DP_WIN;
     struct Regs { unsigned k[DP_WIN]; };
     int M, r0, c0;
-    __device__ __forceinline__ DpDenseMap(const DtwPathParams &p) : M(p.M), r0(0), c0(0) {}
-    __device__ __forceinline__ size_t block(const DtwPathParams &p, int b) const { return (size_t)b * p.N * p.M; }
+    __device__ __forceinline__ DpDenseMap(const DtwParams &p) : M(p.M), r0(0), c0(0) {}
+    __device__ __forceinline__ size_t block(const DtwParams &p, int b) const { return (size_t)b * p.N * p.M; }
     // the window whose last cell is (i, j): rows i - 63 .. i, columns j - 63 .. j
     __device__ __forceinline__ void aim(const unsigned char *, int i, int j) {
         r0 = i - (DP_WIN - 1);
@@ -296,8 +103,8 @@ template <int NB> struct DpBandMap {
     static constexpr int LDS_BYTES = NB * 64 * DP_BATCH * 4;
     struct Regs { unsigned v[NB][DP_BATCH]; };
     int w, W, r0, last, skew;
-    __device__ __forceinline__ DpBandMap(const DtwPathParams &p) : w(p.w), W(2 * p.w + 1), r0(0), last(0), skew(0) {}
-    __device__ __forceinline__ size_t block(const DtwPathParams &p, int b) const { return (size_t)b * p.N * W; }
+    __device__ __forceinline__ DpBandMap(const DtwParams &p) : w(p.w), W(2 * p.w + 1), r0(0), last(0), skew(0) {}
+    __device__ __forceinline__ size_t block(const DtwParams &p, int b) const { return (size_t)b * p.N * W; }
     // the window whose last row is i: rows max(i - 63, 0) .. i, whole: (i - r0 + 1) W contiguous bytes, moved as the
     // aligned words that hold them (the table's base is word-aligned and its size a multiple of 256); `skew` bytes of
     // the first word lie before the window
@@ -342,7 +149,7 @@ template <int NB> struct DpBandMap {
 };
 
 template <class Map>
-__global__ __launch_bounds__(64) void dtwpath_backtrack_kernel(DtwPathParams p) {
+__global__ __launch_bounds__(64) void dtwpath_backtrack_kernel(DtwParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char win[Map::LDS_BYTES];
     __shared__ int note[2 * DP_STEPS];                        // the cells of this window's piece of the path, last first
     const int b = blockIdx.x, lane = threadIdx.x, L = p.L;
@@ -441,17 +248,6 @@ __global__ __launch_bounds__(64) void dtwpath_backtrack_kernel(DtwPathParams p) 
     if (lane == 0) p.length[b] = K;
 }
 
-static int dp_check_penalty(float warp_penalty) {
-    if (!(warp_penalty >= 0.f) || !(warp_penalty < __builtin_huge_valf()))
-        return fail(ALIGNER_EINVAL, "warp_penalty must be finite and not negative");
-    return ALIGNER_OK;
-}
-
-static bool dp_band_shape_ok(int B, int N, int bandwidth) {
-    return B >= 1 && N >= 1 && bandwidth >= 0 && bandwidth <= BD_MAX_W && B <= 65535 &&
-           (long long)N * (2 * bandwidth + 1) < (1ll << 29);
-}
-
 }  // namespace aligner
 
 using namespace aligner;
@@ -470,16 +266,14 @@ int aligner_dtw_path_f32(const float *cost, const int32_t *n_dev, const int32_t 
     if ((path_out == nullptr) != (length_out == nullptr)) return fail(ALIGNER_EINVAL, "null pointer: path_out and length_out go together");
     if (path_out && !workspace) return fail(ALIGNER_EINVAL, "null pointer: a path needs the workspace");
     if (B < 1 || N < 1 || M < 1) return fail(ALIGNER_EINVAL, "bad shape");
-    if (const int rc = dp_check_penalty(warp_penalty)) return rc;
+    if (const int rc = dtw_check_penalty(warp_penalty)) return rc;
     if (bandwidth < -1) return fail(ALIGNER_EINVAL, "bandwidth must be -1 (none) or at least 0");
-    if (B > 65535) return fail(ALIGNER_EDOM, "B=%d too large", B);
-    if (N > SD_MAX_N) return fail(ALIGNER_EDOM, "N=%d too large (<= %d)", N, SD_MAX_N);
-    if ((long long)N * M >= (1ll << 29)) return fail(ALIGNER_EDOM, "N*M=%lld too large (< 2^29)", (long long)N * M);
+    if (const int rc = dtw_dense_domain(B, N, M)) return rc;
     const size_t need = aligner_dtw_path_workspace_bytes(B, N, M);
     if (path_out && workspace_bytes < need)
         return fail(ALIGNER_ENOSPC, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    DtwPathParams p;
+    DtwParams p = {};
     p.cost = cost; p.ns = n_dev; p.ms = m_dev;
     p.pen = warp_penalty;
     p.band = (bandwidth < 0 || bandwidth > SD_NO_BAND) ? SD_NO_BAND : bandwidth;
@@ -489,9 +283,8 @@ int aligner_dtw_path_f32(const float *cost, const int32_t *n_dev, const int32_t 
     p.path = path_out; p.length = length_out;
     p.B = B; p.N = N; p.M = M; p.L = N + M - 1;
     const int NW = (N + 63) / 64;
-    const size_t lds = (size_t)NW * (64 * SD_PITCH + SD_RING) * sizeof(float);
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(dtwpath_forward_kernel), lds));
-    hipLaunchKernelGGL(dtwpath_forward_kernel, dim3(B), dim3(64 * NW), lds, s, p);
+    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(dtw_dense_forward_kernel<DtwHard>), sd_lds_bytes(NW, false)));
+    hipLaunchKernelGGL(dtw_dense_forward_kernel<DtwHard>, dim3(B), dim3(64 * NW), sd_lds_bytes(NW, false), s, p);
     ALIGNER_HIP_CHECK(hipGetLastError());
     if (path_out) {
         hipLaunchKernelGGL(dtwpath_backtrack_kernel<DpDenseMap>, dim3(B), dim3(64), 0, s, p);
@@ -501,7 +294,7 @@ int aligner_dtw_path_f32(const float *cost, const int32_t *n_dev, const int32_t 
 }
 
 size_t aligner_dtw_path_banded_workspace_bytes(int B, int N, int bandwidth) {
-    if (!dp_band_shape_ok(B, N, bandwidth)) return 0;
+    if (!bd_shape_ok(B, N, bandwidth)) return 0;
     return align_up((size_t)B * N * (2 * bandwidth + 1), 256);
 }
 
@@ -513,17 +306,14 @@ int aligner_dtw_path_banded_f32(const float *cost_band, const int32_t *n_dev, co
     if (path_out && !workspace) return fail(ALIGNER_EINVAL, "null pointer: a path needs the workspace");
     if (reinterpret_cast<size_t>(workspace) & 3) return fail(ALIGNER_EINVAL, "the workspace must be 4-byte aligned");
     if (B < 1 || N < 1) return fail(ALIGNER_EINVAL, "bad shape");
-    if (const int rc = dp_check_penalty(warp_penalty)) return rc;
+    if (const int rc = dtw_check_penalty(warp_penalty)) return rc;
     if (bandwidth < 0) return fail(ALIGNER_EINVAL, "bandwidth must be at least 0");
-    if (bandwidth > BD_MAX_W) return fail(ALIGNER_EDOM, "bandwidth=%d too large (<= %d; the dense call takes any band)", bandwidth, BD_MAX_W);
-    if (B > 65535) return fail(ALIGNER_EDOM, "B=%d too large", B);
-    if ((long long)N * (2 * bandwidth + 1) >= (1ll << 29))
-        return fail(ALIGNER_EDOM, "N*W=%lld too large (< 2^29)", (long long)N * (2 * bandwidth + 1));
+    if (const int rc = dtw_band_domain(B, N, bandwidth, "the dense call takes any band")) return rc;
     const size_t need = aligner_dtw_path_banded_workspace_bytes(B, N, bandwidth);
     if (path_out && workspace_bytes < need)
         return fail(ALIGNER_ENOSPC, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    DtwPathParams p;
+    DtwParams p = {};
     p.cost = cost_band; p.ns = n_dev; p.ms = m_dev;
     p.pen = warp_penalty;
     p.band = bandwidth; p.w = bandwidth;
@@ -531,8 +321,8 @@ int aligner_dtw_path_banded_f32(const float *cost_band, const int32_t *n_dev, co
     p.dec = path_out ? static_cast<unsigned char *>(workspace) : nullptr;
     p.path = path_out; p.length = length_out;
     p.B = B; p.N = N; p.M = N + bandwidth; p.L = 2 * N + bandwidth - 1;
-    if (bandwidth <= 63) hipLaunchKernelGGL(dtwpath_band_forward_kernel<64>, dim3(B), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL(dtwpath_band_forward_kernel<128>, dim3(B), dim3(64), 0, s, p);
+    if (bandwidth <= 63) hipLaunchKernelGGL((dtw_band_forward_kernel<DtwHard, 64>), dim3(B), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((dtw_band_forward_kernel<DtwHard, 128>), dim3(B), dim3(64), 0, s, p);
     ALIGNER_HIP_CHECK(hipGetLastError());
     if (path_out) {
         if (bandwidth <= 63) hipLaunchKernelGGL(dtwpath_backtrack_kernel<DpBandMap<1>>, dim3(B), dim3(64), 0, s, p);

@@ -4,14 +4,8 @@
 //
 //     R[i,j] = D[i,j] + softmin_gamma(R[i-1,j-1], R[i-1,j] + p, R[i,j-1] + p)        value = R[n-1,m-1]
 //
-// One workgroup per utterance, one lane per row, a wave per 64 rows, and nothing shared between workgroups.  The
-// lanes are skewed: at its local step s wave w's lane l sits on column s - l of row 64 w + l, so R[i-1,j] is what the
-// lane below computed in the step before (one wave_shr per step), R[i-1,j-1] what it handed over the step before
-// that, and R[i,j-1] the lane's own register.  A wave's last row reaches the next wave through a ring in LDS; the
-// waves run SD_LAG tiles of SD_TW steps apart (the skew makes a wave's last row 63 steps late) with one barrier per
-// tile.  Costs come through LDS in the skewed order -- position c of row r of tile t is column t SD_TW + c - r, a
-// 64-byte segment of the row in memory -- at a pitch of SD_TW + 1 floats, so the 64 lanes of a step read 64 banks;
-// R (for the gradient) leaves through the same tile.
+// Forward is dtw_forward.h's dense kernel (one workgroup per utterance, a lane per row on the skewed pipeline, a wave
+// per 64 rows) with the soft cell of softdtw_cell.h; R (for the gradient) leaves through its tile.
 //
 // Arithmetic: base-2 logs with log2(e) / gamma folded into the costs on their way in, "+inf" the finite SD_BIG
 // (it absorbs every addend, nothing computes inf - inf), every cell's result clamped to [-SD_BIG, SD_BIG].
@@ -26,109 +20,11 @@
 #include "device.h"
 #include "softdtw_cell.h"
 #include "dtw_schedule.h"
+#include "dtw_forward.h"
 
 namespace aligner {
 
-struct SoftDtwParams {
-    const float *cost;      // [B,N,M]
-    const int   *ns, *ms;   // [B] or null
-    float scale;            // log2(e) / gamma
-    float pen;              // warp penalty, scaled
-    float unscale;          // gamma ln 2
-    int   band;             // SD_NO_BAND: none
-    float *value;           // [B]
-    float *grad;            // [B,N,M]: R (scaled) after forward, E after backward; null: value only
-    float *fin;             // workspace [B]: R[n-1,m-1] scaled, SD_BIG without an alignment
-    int B, N, M;
-};
-
-__global__ __launch_bounds__(SD_MAX_N) void softdtw_forward_kernel(SoftDtwParams p) {
-    extern __shared__ __attribute__((aligned(16))) float sd_smem[];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), NW = blockDim.x >> 6;
-    int n, m;
-    if (!sd_lengths(p, b, n, m)) {
-        if (tid == 0) { p.value[b] = __builtin_huge_valf(); p.fin[b] = SD_BIG; }
-        return;
-    }
-    const int nw = (n + 63) >> 6;                             // waves that own rows of this utterance
-    const bool active = w < nw;
-    float *tile = sd_smem + w * 64 * SD_PITCH;                // [64][SD_PITCH] this wave's costs, then its R
-    float *ring = sd_smem + NW * 64 * SD_PITCH;               // [NW][SD_RING] each wave's last row, by column
-    const int ntl = (m + 64 + SD_TW - 1) / SD_TW;             // steps 0 .. m + 62 reach every cell of 64 skewed rows
-    const int nph = ntl + SD_LAG * (nw - 1) + 1;
-    const size_t ubase = (size_t)b * p.N * p.M;
-    const float *cost = p.cost + ubase;
-    float *R = p.grad ? p.grad + ubase : nullptr;
-    const int i = 64 * w + lane;
-    int jlo, jhi;
-    sd_row_span(i, n, m, p.band, jlo, jhi);
-    // the movers' element k of a tile: row r0 + SD_RS k of the wave at position c0, SD_RS rows a pass (a 64-byte segment
-    // of a row per 16 lanes); its column at tile t is t SD_TW + col0 - SD_RS k and its place in memory moves by kstride
-    const int r0 = lane / SD_TW, c0 = lane % SD_TW, row0 = 64 * w + r0, col0 = c0 - r0;
-    const int off0 = row0 * p.M + col0, kstride = SD_RS * (p.M - 1), lds0 = r0 * SD_PITCH + c0;
-    float prev = SD_BIG;                                      // R[i,j-1]
-    float upprev = i == 0 ? 0.f : SD_BIG;                     // R[i-1,j-1]; R[-1,-1] = 0
-    float fin = SD_BIG;
-    for (int ph = 0; ph < nph; ++ph) {
-        const int t = ph - SD_LAG * w - 1;                    // (the phase before a wave's first tile stages that tile)
-        const bool ldnext = active && t + 1 >= 0 && t + 1 < ntl;
-        float v[SD_TW];
-        if (ldnext) {
-#pragma unroll
-            for (int k = 0; k < SD_TW; ++k) {
-                const int row = row0 + SD_RS * k, col = (t + 1) * SD_TW + col0 - SD_RS * k;
-                float d = SD_BIG;
-                if (row < n && col >= 0 && col < m) d = cost[off0 + (t + 1) * SD_TW + k * kstride];
-                v[k] = sd_cost_in(d, p.scale);
-            }
-        }
-        if (active && t >= 0 && t < ntl) {
-            float bv = SD_BIG;                                // the row above this wave's first, columns of this tile
-            if (w > 0 && lane < SD_TW) {
-                const int col = t * SD_TW + lane;
-                if (col < m) bv = ring[(w - 1) * SD_RING + (col & (SD_RING - 1))];
-            }
-            float dv[SD_TW];                                  // (read up front: behind the stores of R below, the compiler
-#pragma unroll                                                //  keeps each read in its own step and waits for it there)
-            for (int c = 0; c < SD_TW; ++c) dv[c] = tile[lane * SD_PITCH + c];
-#pragma unroll
-            for (int c = 0; c < SD_TW; ++c) {
-                const int j = t * SD_TW + c - lane;
-                const float d = dv[c];
-                const float up = sd_from_below(sd_lane(bv, c), prev);
-                float cur = sd_cell(upprev, up, prev, p.pen, d);
-                const bool valid = j >= jlo && j <= jhi;
-                cur = valid ? cur : SD_BIG;
-                if (R) tile[lane * SD_PITCH + c] = cur;
-                // (columns below 0 land on entries nobody reads yet: the next wave starts SD_LAG tiles later and masks them)
-                if (lane == 63) ring[w * SD_RING + (j & (SD_RING - 1))] = cur;
-                if (valid && j == m - 1 && i == n - 1) fin = cur;
-                upprev = up;
-                prev = cur;
-            }
-            if (R) {
-                sd_wave_lds_sync();
-#pragma unroll
-                for (int k = 0; k < SD_TW; ++k) {
-                    const int row = row0 + SD_RS * k, col = t * SD_TW + col0 - SD_RS * k;
-                    if (row < n && col >= 0 && col < m) R[off0 + t * SD_TW + k * kstride] = tile[lds0 + k * SD_RS * SD_PITCH];
-                }
-            }
-        }
-        if (ldnext) {
-#pragma unroll
-            for (int k = 0; k < SD_TW; ++k) tile[lds0 + k * SD_RS * SD_PITCH] = v[k];
-        }
-        lds_barrier();
-    }
-    if (i == n - 1) {
-        p.fin[b] = fin;
-        p.value[b] = fin < 0.5f * SD_BIG ? fin * p.unscale : __builtin_huge_valf();
-    }
-}
-
-__global__ __launch_bounds__(SD_MAX_N) void softdtw_backward_kernel(SoftDtwParams p) {
+__global__ __launch_bounds__(SD_MAX_N) void softdtw_backward_kernel(DtwParams p) {
     extern __shared__ __attribute__((aligned(16))) float sd_smem[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), NW = blockDim.x >> 6;
@@ -221,10 +117,6 @@ __global__ __launch_bounds__(SD_MAX_N) void softdtw_backward_kernel(SoftDtwParam
     }
 }
 
-static size_t sd_lds_bytes(int NW, bool backward) {
-    return (size_t)NW * ((backward ? 65 : 64) * SD_PITCH + SD_RING) * sizeof(float);
-}
-
 }  // namespace aligner
 
 using namespace aligner;
@@ -243,29 +135,22 @@ int aligner_soft_dtw_f32(const float *cost, const int32_t *n_dev, const int32_t 
     if (!cost || !value_out || !workspace) return fail(ALIGNER_EINVAL, "null pointer");
     if (B < 1 || N < 1 || M < 1) return fail(ALIGNER_EINVAL, "bad shape");
     if (!(gamma > 0.f) || !(gamma < __builtin_huge_valf())) return fail(ALIGNER_EINVAL, "gamma must be positive and finite");
-    if (!(warp_penalty >= 0.f) || !(warp_penalty < __builtin_huge_valf()))
-        return fail(ALIGNER_EINVAL, "warp_penalty must be finite and not negative");
+    if (const int rc = dtw_check_penalty(warp_penalty)) return rc;
     if (bandwidth < -1) return fail(ALIGNER_EINVAL, "bandwidth must be -1 (none) or at least 0");
-    if (B > 65535) return fail(ALIGNER_EDOM, "B=%d too large", B);
-    if (N > SD_MAX_N) return fail(ALIGNER_EDOM, "N=%d too large (<= %d)", N, SD_MAX_N);
-    if ((long long)N * M >= (1ll << 29)) return fail(ALIGNER_EDOM, "N*M=%lld too large (< 2^29)", (long long)N * M);
+    if (const int rc = dtw_dense_domain(B, N, M)) return rc;
     const size_t need = aligner_soft_dtw_workspace_bytes(B, N, M, grad_out != nullptr);
     if (workspace_bytes < need)
         return fail(ALIGNER_ENOSPC, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SoftDtwParams p;
+    DtwParams p = {};
     p.cost = cost; p.ns = n_dev; p.ms = m_dev;
-    const double scale = 1.4426950408889634 / (double)gamma;
-    p.scale = (float)scale;
-    const double pen = (double)warp_penalty * scale;
-    p.pen = pen < (double)SD_BIG ? (float)pen : SD_BIG;
-    p.unscale = (float)((double)gamma * 0.6931471805599453);
+    dtw_soft_scaling(p, gamma, warp_penalty);
     p.band = (bandwidth < 0 || bandwidth > SD_NO_BAND) ? SD_NO_BAND : bandwidth;
     p.value = value_out; p.grad = grad_out; p.fin = static_cast<float *>(workspace);
     p.B = B; p.N = N; p.M = M;
     const int NW = (N + 63) / 64;
-    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(softdtw_forward_kernel), sd_lds_bytes(NW, false)));
-    hipLaunchKernelGGL(softdtw_forward_kernel, dim3(B), dim3(64 * NW), sd_lds_bytes(NW, false), s, p);
+    ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(dtw_dense_forward_kernel<DtwSoft>), sd_lds_bytes(NW, false)));
+    hipLaunchKernelGGL(dtw_dense_forward_kernel<DtwSoft>, dim3(B), dim3(64 * NW), sd_lds_bytes(NW, false), s, p);
     ALIGNER_HIP_CHECK(hipGetLastError());
     if (grad_out) {
         ALIGNER_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void *>(softdtw_backward_kernel), sd_lds_bytes(NW, true)));

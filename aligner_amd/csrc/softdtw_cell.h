@@ -5,12 +5,14 @@
 // Base-2 logs with log2(e) / gamma folded into the costs on their way in, "+inf" the finite SD_BIG (it absorbs every
 // addend, nothing computes inf - inf), every cell's result clamped to [-SD_BIG, SD_BIG].  Backward is pushed: a cell
 // hands its E times the softmin's own weights 2^(mn - pred) / sum to its three predecessors.
+//
+// DtwSoft is this arithmetic as the cell policy of the forward kernels (dtw_forward.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace aligner {
+#include "dtw_schedule.h"
 
-constexpr float SD_BIG = 1e30f;                           // "+inf" in scaled units
+namespace aligner {
 
 // lane i <- src[lane i-1], lane 0 gets `edge` (wave_shr:1); lane i <- src[lane i+1], lane 63 gets `edge` (wave_shl:1)
 __device__ __forceinline__ float sd_from_below(float edge, float src) {
@@ -57,5 +59,25 @@ __device__ __forceinline__ void sd_push(float diag, float up, float left, float 
     cu = q * wb;
     cl = q * wc;
 }
+
+// The soft cell for dtw_forward.h: R (scaled) is what a cell keeps, in the tile and in the table; R[n-1,m-1] goes to the
+// workspace for the backward kernel and, unscaled, to the value.
+struct DtwSoft {
+    using Out = float;
+    static constexpr bool TILE_HOLDS_VALUE = true;
+    static __device__ __forceinline__ float none() { return SD_BIG; }
+    static __device__ __forceinline__ float in(const DtwParams &p, float d) { return sd_cost_in(d, p.scale); }
+    static __device__ __forceinline__ float cell(const DtwParams &p, float diag, float up, float left, float d, int &k) {
+        k = 0;
+        return sd_cell(diag, up, left, p.pen, d);
+    }
+    static __device__ __forceinline__ float keep(float cur, int) { return cur; }
+    static __device__ __forceinline__ float *table(const DtwParams &p) { return p.grad; }
+    static __device__ __forceinline__ float out(float x) { return x; }
+    static __device__ __forceinline__ void finish(const DtwParams &p, int b, float fin) {
+        p.fin[b] = fin;
+        p.value[b] = fin < 0.5f * SD_BIG ? fin * p.unscale : __builtin_huge_valf();
+    }
+};
 
 }  // namespace aligner
