@@ -209,7 +209,7 @@ __device__ __forceinline__ void cg_store_f32(const ConvGemmParams &p, const cg_f
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 v[r] += bv;
-                if (p.relu) v[r] = fmaxf(v[r], 0.f);
+                if (p.relu) v[r] = relu_nan(v[r]);
             }
             if (vec) {
                 if (f < p.T) *reinterpret_cast<cg_f32x4 *>(yr + f) = v;       // T % 4 == 0: a quad is all in or all out
@@ -254,7 +254,7 @@ __device__ __forceinline__ void cg_store_split(const ConvGemmParams &p, const cg
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float v = acc[a][n][r] + bv[r];
-                if (p.relu) v = fmaxf(v, 0.f);
+                if (p.relu) v = relu_nan(v);
                 v = and_mask(v, (f < p.T && ob + r < p.Cout) ? ~0u : 0u);
                 __bf16 hh, ll;
                 split_bf16(v, hh, ll);
@@ -746,7 +746,7 @@ __device__ __forceinline__ void cg_store_lds(unsigned char *dst, int nch_next, c
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float v = acc[a][n][r] + bv[r];
-                if (L.relu) v = fmaxf(v, 0.f);
+                if (L.relu) v = relu_nan(v);
                 v = and_mask(v, keep[r] & fin);
                 __bf16 hh, ll;
                 split_bf16(v, hh, ll);
@@ -1137,7 +1137,7 @@ __global__ __launch_bounds__(WO * WT * 64) void conv1d_prepared_kernel(const flo
                 const int t = t0 + wt + 32 * c + l31;
                 if (t < T) {
                     float v = acc[a][c][e] + bv;
-                    if (relu) v = fmaxf(v, 0.f);
+                    if (relu) v = relu_nan(v);
                     y[((size_t)b * Cout + o) * T + t] = v;
                 }
             }

@@ -17,6 +17,11 @@ __device__ __forceinline__ float and_mask(float v, unsigned m) {
     return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & m);
 }
 
+// ReLU that keeps NaN, as torch.relu does (fmaxf(NaN, 0) is 0: a NaN activation would vanish after one layer and the
+// loss of a diverged run stay finite).  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950, where the select
+// v < 0 ? 0 : v is a compare and a v_cndmask per element (C3's step 214 -> 216 us)
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
 // v = hi + lo in two bf16 halves (lo: the rounding error of hi, itself rounded): a product of two such pairs as
 // hi*hi + hi*lo + lo*hi with fp32 accumulation is ~2^-16 relative, at the bf16 MFMA rate
 __device__ __forceinline__ void split_bf16(float v, __bf16 &hi, __bf16 &lo) {

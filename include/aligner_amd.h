@@ -512,6 +512,17 @@ int aligner_gauss_upsample_backward_f32(const float *h_dev, const float *centre_
  * fragment order): aligner_conv1d_prepare_f32 writes aligner_conv1d_prepared_bytes(Cout,Cin,K) bytes,
  * aligner_conv1d_prepared_f32 consumes them.  Products are hi*hi + hi*lo + lo*hi in fp32 accumulators
  * (~2^-16 relative per product).  This is the fast path of the encoders: prepare per weight update.
+ *
+ * Numerics, the same for every entry point and kernel form of this section, per layer and per output element:
+ *   |y - exact| <= (3 * 2^-16 + accumulation) * (|bias[o]| + sum_{i,k} |w[o,i,k]| |x[b,i,t+k-K/2]|)
+ * 3 * 2^-16 is the worst case of one split product (the dropped lo*lo and the two rounding terms), whatever the input's
+ * scale, offset or dynamic range and whatever the fan-in; the accumulation term is that of an fp32 sum over the
+ * Cin * K products in the matrix cores' order (a few 2^-24 to a few 10 * 2^-24: tests/conv_oracle.py tabulates it).
+ * A stack carries each layer's error through the next layer's |w| (ReLU is 1-Lipschitz).
+ * Non-finite activations: a NaN gives NaN in its receptive field, in every output channel, and PASSES THROUGH ReLU
+ * (as torch.relu; every other element keeps the bits it would have had).  +-Inf activations come out as NaN, not as
+ * +-Inf (the split takes lo = v - hi = inf - inf), in the same receptive field.
+ * The result never depends on what the workspace held before the call.
  */
 size_t aligner_conv1d_prepared_bytes(int Cout, int Cin, int K);
 int aligner_conv1d_prepare_f32(const float *w_dev, void *prepared_dev, size_t prepared_bytes,
