@@ -27,6 +27,8 @@ from .l1cost import l1_cost, l1_cost_backward, soft_dtw_l1_loss  # noqa: F401
 from .banddtw import (band_to_dense, dense_to_band, l1_cost_banded, l1_cost_banded_backward, soft_dtw_banded,  # noqa: F401
                       soft_dtw_banded_loss, soft_dtw_l1_banded_loss)
 from .dtwpath import DtwPath, dtw_path, dtw_path_banded, dtw_path_l1, path_to_dense  # noqa: F401
+from .l2cost import (dtw_path_l2, l2_cost, l2_cost_backward, l2_cost_banded, l2_cost_banded_backward, mcd_dtw,  # noqa: F401
+                     soft_dtw_l2_banded_loss, soft_dtw_l2_loss)
 
 __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status",
            "soft_attention", "soft_attention_backward", "conv1d", "conv1d_backward", "alignment_encoder", "AlignmentEncoderParams",
@@ -39,6 +41,8 @@ __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status"
            "dense_to_band", "band_to_dense", "soft_dtw_banded", "soft_dtw_banded_loss", "l1_cost_banded",
            "l1_cost_banded_backward", "soft_dtw_l1_banded_loss",
            "dtw_path", "dtw_path_banded", "dtw_path_l1", "path_to_dense", "DtwPath",
+           "l2_cost", "l2_cost_backward", "soft_dtw_l2_loss", "l2_cost_banded", "l2_cost_banded_backward",
+           "soft_dtw_l2_banded_loss", "dtw_path_l2", "mcd_dtw",
            "install_dropin"]
 
 

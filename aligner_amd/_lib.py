@@ -123,6 +123,10 @@ SIGNATURES = {
     "aligner_soft_dtw_banded_f32": (_i, [_vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "aligner_l1_cost_banded_f32": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _i, _i, _i, _i, _vp]),
     "aligner_l1_cost_banded_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "aligner_l2_cost_f32": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp, _i, _i, _i, _i, _vp]),
+    "aligner_l2_cost_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "aligner_l2_cost_banded_f32": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp, _i, _i, _i, _i, _vp]),
+    "aligner_l2_cost_banded_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "aligner_dtw_path_workspace_bytes": (_sz, [_i, _i, _i]),
     "aligner_dtw_path_f32": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "aligner_dtw_path_banded_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from ._operands import (check_reduction, dp_parameters, f32c, lengths, one_gpu, pred_target_shapes, ptr, reduced,
                         stream)
+from .l1cost import L1, L2
 
 MAX_BANDWIDTH = 127
 
@@ -156,14 +157,8 @@ def _checked_cost(pred, target, bandwidth, scale, also=()):
     return B, C, N, target.shape[2], w, scale, dev
 
 
-def l1_cost_banded(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None,
-                   m: Optional[torch.Tensor] = None, bandwidth: int = 60, scale: float = 1.0) -> torch.Tensor:
-    """cost_band [B,N,W], fp32: scale sum_c |pred[b,c,i] - target[b,c,j]| on the cells that exist, exactly 0 elsewhere;
-    every element is written.
-
-    pred [B,C,N], target [B,C,M]: GPU tensors (bf16 / fp16 are cast, non-contiguous ones copied); n / m [B]: the lengths
-    (None: N / M; m is clamped to M and to N + w).  bandwidth <= 127, B <= 65535, C <= 4096, N*W < 2^29 (an AlignerError
-    of code EDOM beyond).  Not attached to autograd.  Empty shapes return without a launch.  Asynchronous."""
+def _cost_banded(kind, pred, target, n, m, bandwidth, scale) -> torch.Tensor:
+    """l1_cost_banded() / l2_cost_banded(): the [B,N,W] table of `kind` (l1cost.py names the kinds)."""
     B, C, N, M, w, scale, dev = _checked_cost(pred, target, bandwidth, scale)
     nn = lengths(n, B, dev, "n")
     mm = lengths(m, B, dev, "m")
@@ -174,19 +169,31 @@ def l1_cost_banded(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.T
     p, t = f32c(pred), f32c(target)
     cost = torch.empty((B, N, 2 * w + 1), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.aligner_l1_cost_banded_f32(p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), w, scale, cost.data_ptr(),
-                                                  B, C, N, M, stream(dev)))
+        if kind == L1:
+            rc = lib.aligner_l1_cost_banded_f32(p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), w, scale, cost.data_ptr(),
+                                                B, C, N, M, stream(dev))
+        else:
+            rc = lib.aligner_l2_cost_banded_f32(p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), w, scale, int(kind == L2),
+                                                cost.data_ptr(), B, C, N, M, stream(dev))
+        _lib.check(rc)
     return cost
 
 
-def l1_cost_banded_backward(grad_band: torch.Tensor, pred: torch.Tensor, target: torch.Tensor,
-                            n: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None, scale: float = 1.0,
-                            row_scale: Optional[torch.Tensor] = None, want: Tuple[bool, bool] = (True, True)
-                            ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """(dpred [B,C,N] or None, dtarget [B,C,M] or None) of l1_cost_backward() with G = grad_band [B,N,W] in band storage
-    (the bandwidth is (W - 1) / 2).  row_scale [B]: the per-utterance factor (None: 1).  G is never read as a value
-    where no cell exists.  One owner per output element, no atomics: the same bits on every call, and each output has
-    the same bits whether or not the other is asked for."""
+def l1_cost_banded(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None,
+                   m: Optional[torch.Tensor] = None, bandwidth: int = 60, scale: float = 1.0) -> torch.Tensor:
+    """cost_band [B,N,W], fp32: scale sum_c |pred[b,c,i] - target[b,c,j]| on the cells that exist, exactly 0 elsewhere;
+    every element is written.
+
+    pred [B,C,N], target [B,C,M]: GPU tensors (bf16 / fp16 are cast, non-contiguous ones copied); n / m [B]: the lengths
+    (None: N / M; m is clamped to M and to N + w).  bandwidth <= 127, B <= 65535, C <= 4096, N*W < 2^29 (an AlignerError
+    of code EDOM beyond).  Not attached to autograd.  Empty shapes return without a launch.  Asynchronous."""
+    return _cost_banded(L1, pred, target, n, m, bandwidth, scale)
+
+
+def _cost_banded_backward(kind, grad_band, pred, target, n, m, scale, row_scale, want):
+    """l1_cost_banded_backward() / l2_cost_banded_backward(): (dpred, dtarget) of `kind` (L1 or L2)."""
+    if kind not in (L1, L2):
+        raise ValueError("the root of the Euclidean cost has no gradient: train on the squared cost")
     if not isinstance(grad_band, torch.Tensor) or grad_band.dim() != 3 or grad_band.shape[2] % 2 == 0:
         raise ValueError("grad_band must be a [B,N,W] tensor with an odd W = 2 bandwidth + 1")
     B, C, N, M, w, scale, dev = _checked_cost(pred, target, (grad_band.shape[2] - 1) // 2, scale, also=((grad_band, "grad_band"),))
@@ -210,39 +217,62 @@ def l1_cost_banded_backward(grad_band: torch.Tensor, pred: torch.Tensor, target:
     lib = _lib.load()
     g, p, t = f32c(grad_band), f32c(pred), f32c(target)
     with torch.cuda.device(dev):
-        _lib.check(lib.aligner_l1_cost_banded_backward_f32(g.data_ptr(), p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), w, scale,
-                                                           ptr(rs), ptr(dpred), ptr(dtarget), B, C, N, M, stream(dev)))
+        fn = lib.aligner_l1_cost_banded_backward_f32 if kind == L1 else lib.aligner_l2_cost_banded_backward_f32
+        _lib.check(fn(g.data_ptr(), p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), w, scale, ptr(rs), ptr(dpred), ptr(dtarget),
+                      B, C, N, M, stream(dev)))
     return dpred, dtarget
 
 
-class _SoftDtwL1BandedLoss(torch.autograd.Function):
+def l1_cost_banded_backward(grad_band: torch.Tensor, pred: torch.Tensor, target: torch.Tensor,
+                            n: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None, scale: float = 1.0,
+                            row_scale: Optional[torch.Tensor] = None, want: Tuple[bool, bool] = (True, True)
+                            ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(dpred [B,C,N] or None, dtarget [B,C,M] or None) of l1_cost_backward() with G = grad_band [B,N,W] in band storage
+    (the bandwidth is (W - 1) / 2).  row_scale [B]: the per-utterance factor (None: 1).  G is never read as a value
+    where no cell exists.  One owner per output element, no atomics: the same bits on every call, and each output has
+    the same bits whether or not the other is asked for."""
+    return _cost_banded_backward(L1, grad_band, pred, target, n, m, scale, row_scale, want)
+
+
+def _dp_columns(m, pred, target):
+    """m as the band-storage DP needs it: the cost knows the target's M, the DP is told through m."""
+    if m is not None:
+        return torch.as_tensor(m).clamp(max=target.shape[2])
+    return torch.full((pred.shape[0],), target.shape[2], dtype=torch.int32, device=pred.device)
+
+
+class _SoftDtwCostBandedLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, target, n, m, gamma, warp_penalty, bandwidth, scale):
-        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    def forward(ctx, kind, pred, target, n, m, gamma, warp_penalty, bandwidth, scale):
+        need = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         # the band cost tensor lives for these lines: the DP's backward reads R only, and E overwrites R in place
-        cost = l1_cost_banded(pred, target, n, m, bandwidth, scale)
-        if m is not None:                           # (the cost knows the target's M; the DP is told through m)
-            m = torch.as_tensor(m).clamp(max=target.shape[2])
-        else:
-            m = torch.full((pred.shape[0],), target.shape[2], dtype=torch.int32, device=pred.device)
+        cost = _cost_banded(kind, pred, target, n, m, bandwidth, scale)
+        m = _dp_columns(m, pred, target)
         value, E = soft_dtw_banded(cost, n, m, gamma, warp_penalty, want_grad=need)
         del cost
         if need:
             ctx.save_for_backward(pred, target, E)
         ctx.lengths = (n, m)
-        ctx.scale = scale
+        ctx.kind, ctx.scale = kind, scale
         return value
 
     @staticmethod
     def backward(ctx, g_value):
-        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        want = (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         if not (want[0] or want[1]) or g_value is None:
-            return (None,) * 8
+            return (None,) * 9
         pred, target, E = ctx.saved_tensors
         n, m = ctx.lengths
-        dpred, dtarget = l1_cost_banded_backward(E, pred, target, n, m, ctx.scale, row_scale=g_value, want=want)
-        return (None if dpred is None else dpred.to(pred.dtype), None if dtarget is None else dtarget.to(target.dtype),
+        dpred, dtarget = _cost_banded_backward(ctx.kind, E, pred, target, n, m, ctx.scale, g_value, want)
+        return (None, None if dpred is None else dpred.to(pred.dtype), None if dtarget is None else dtarget.to(target.dtype),
                 None, None, None, None, None, None)
+
+
+def _soft_dtw_cost_banded_loss(kind, pred, target, n, m, gamma, warp_penalty, bandwidth, scale, reduction, zero_infinity):
+    check_reduction(reduction)
+    _bandwidth(bandwidth)
+    value = _SoftDtwCostBandedLoss.apply(kind, pred, target, n, m, gamma, warp_penalty, bandwidth, scale)
+    return reduced(value, reduction, zero_infinity)
 
 
 def soft_dtw_l1_banded_loss(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None,
@@ -255,7 +285,4 @@ def soft_dtw_l1_banded_loss(pred: torch.Tensor, target: torch.Tensor, n: Optiona
     lengths: [B,N,2w+1] where the dense function keeps [B,N,M].  Gradients come back in the inputs' dtypes, None for
     an input that does not require one.  Any N (no 1024-row limit); bandwidth <= 127, beyond which soft_dtw_l1_loss()
     is the path.  Parallel Tacotron 2: gamma 0.05, warp_penalty 128, bandwidth 60."""
-    check_reduction(reduction)
-    _bandwidth(bandwidth)
-    value = _SoftDtwL1BandedLoss.apply(pred, target, n, m, gamma, warp_penalty, bandwidth, scale)
-    return reduced(value, reduction, zero_infinity)
+    return _soft_dtw_cost_banded_loss(L1, pred, target, n, m, gamma, warp_penalty, bandwidth, scale, reduction, zero_infinity)

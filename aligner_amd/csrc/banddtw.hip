@@ -12,10 +12,13 @@
 // without a cell and leave; wave 0 sweeps.
 //
 // The L1 cost and its gradient in the same layout follow the kernels of l1cost.hip: formulas, sign(0) = 0, one owner
-// per output element, a fixed order of summation, G selected (never multiplied) by "the cell exists".
+// per output element, a fixed order of summation, G selected (never multiplied) by "the cell exists".  Like them they
+// are written once over the cost kind (costkind.h) and add the channels in the same order with the same operations:
+// on the cells that exist the band table has the bits of the dense one, whatever the kind.
 #include "common.h"
 #include "device.h"
 #include "softdtw_cell.h"
+#include "costkind.h"
 #include "dtw_schedule.h"
 #include "dtw_forward.h"
 
@@ -161,16 +164,16 @@ __global__ __launch_bounds__(64 * BD_BWD_WAVES) void banddtw_backward_kernel(Dtw
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// the L1 cost in band storage and its gradient
+// the cost of a kind (costkind.h) in band storage and its gradient
 
-__device__ __forceinline__ float bc_signed(float p, float t, float g) { return p > t ? g : (p < t ? -g : 0.f); }
 __device__ __forceinline__ float bc_lane(float v, int l) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
 
 // A wave owns rows i0 .. i0 + 15 and the 64 columns j = i0 - w + 64 ct + lane: one target load per channel feeds
 // 16 cells, and row i0 + r stores d = 64 ct + lane - r, contiguous over the lanes.
-__global__ __launch_bounds__(256) void band_l1_cost_kernel(
+template <class Kind>
+__global__ __launch_bounds__(256) void bc_cost_kernel(
         const float *__restrict__ pred, const float *__restrict__ target, const int *__restrict__ ns,
         const int *__restrict__ ms, int w, float scale, float *__restrict__ cost, int C, int N, int M, int nch) {
     const int b = blockIdx.z, lane = threadIdx.x & 63;
@@ -192,20 +195,21 @@ __global__ __launch_bounds__(256) void band_l1_cost_kernel(
         for (int c = 0; c < C; ++c, t += M, p += N) {
             const float tv = *t, pl = *p;
 #pragma unroll
-            for (int r = 0; r < BC_RB; ++r) acc[r] = acc[r] + __builtin_fabsf(tv - bc_lane(pl, r));
+            for (int r = 0; r < BC_RB; ++r) acc[r] = Kind::term(tv, bc_lane(pl, r), acc[r]);
         }
     }
     float *out = cost + ((size_t)b * N + i0) * W;
 #pragma unroll
     for (int r = 0; r < BC_RB; ++r) {
         const int i = i0 + r, d = 64 * ct + lane - r;
-        if (i < N && d >= 0 && d < W) out[r * W + d] = (i < n && j >= 0 && j < m) ? acc[r] * scale : 0.f;
+        if (i < N && d >= 0 && d < W) out[r * W + d] = (i < n && j >= 0 && j < m) ? Kind::finish(acc[r], scale) : 0.f;
     }
 }
 
 // dtarget: a wave owns 64 columns and BC_CC channels and walks the rows j0 - w .. j0 + 63 + w; lane j reads
 // G[i, j - i + w], contiguous over the lanes.
-__global__ __launch_bounds__(256) void band_l1_dtarget_kernel(
+template <class Kind>
+__global__ __launch_bounds__(256) void bc_dtarget_kernel(
         const float *__restrict__ G, const float *__restrict__ pred, const float *__restrict__ target,
         const int *__restrict__ ns, const int *__restrict__ ms, int w, float scale, const float *__restrict__ row_scale,
         float *__restrict__ dtarget, int C, int N, int M) {
@@ -238,17 +242,17 @@ __global__ __launch_bounds__(256) void band_l1_dtarget_kernel(
                 const bool ok = i < ihi && j < m && d >= 0 && d < W;
                 gv[r] = and_mask(g[(i < N ? i : N - 1) * W + (d < 0 ? 0 : (d < W ? d : W - 1))], ok ? ~0u : 0u);
             }
-            const int rl = ib + lane < N ? ib + lane : N - 1;
+            const int rl = ib + lane < ihi ? ib + lane : ihi - 1;         // (a row of the utterance: costkind.h)
 #pragma unroll
             for (int cc = 0; cc < BC_CC; ++cc) {
                 const float pl = p[(size_t)(cc < cmax ? cc : cmax) * N + rl];
 #pragma unroll
-                for (int r = 0; r < BC_TR; ++r) acc[cc] = acc[cc] + bc_signed(bc_lane(pl, r), tv[cc], gv[r]);
+                for (int r = 0; r < BC_TR; ++r) acc[cc] = Kind::back(bc_lane(pl, r), tv[cc], gv[r], acc[cc]);
             }
         }
     }
     if (j >= M) return;
-    const float k = -(scale * (row_scale ? row_scale[b] : 1.f));
+    const float k = -Kind::factor(scale, row_scale ? row_scale[b] : 1.f);
     float *out = dtarget + ((size_t)b * C + c0) * M + j;
 #pragma unroll
     for (int cc = 0; cc < BC_CC; ++cc)
@@ -257,7 +261,8 @@ __global__ __launch_bounds__(256) void band_l1_dtarget_kernel(
 
 // dpred: a wave owns BC_PR rows and BC_CC channels; lane l sums the cells d = l, l + 64, ... of each row (G and
 // target both contiguous over the lanes), and the 64 lanes' sums meet in LDS, added in lane order.
-__global__ __launch_bounds__(64) void band_l1_dpred_kernel(
+template <class Kind>
+__global__ __launch_bounds__(64) void bc_dpred_kernel(
         const float *__restrict__ G, const float *__restrict__ pred, const float *__restrict__ target,
         const int *__restrict__ ns, const int *__restrict__ ms, int w, float scale, const float *__restrict__ row_scale,
         float *__restrict__ dpred, int C, int N, int M) {
@@ -290,12 +295,12 @@ __global__ __launch_bounds__(64) void band_l1_dpred_kernel(
             const int i = i0 + r, j = i + d - w;
             const bool ok = i < n && d < W && j >= 0 && j < m;
             const float gv = and_mask(gb[(i < N ? i : N - 1) * W + (d < W ? d : W - 1)], ok ? ~0u : 0u);
-            const int jc = j < 0 ? 0 : (j < M ? j : M - 1);
+            const int jc = j < 0 ? 0 : (j < m ? j : m - 1);               // (a column of the utterance: costkind.h)
 #pragma unroll
             for (int cc = 0; cc < BC_CC; ++cc) {
                 const int ch = cc < cmax ? cc : cmax;
                 const float pv = pb[(size_t)ch * N + (i < N ? i : N - 1)];
-                acc[cc][r] = acc[cc][r] + bc_signed(pv, tb[(size_t)ch * M + jc], gv);
+                acc[cc][r] = Kind::back(pv, tb[(size_t)ch * M + jc], gv, acc[cc][r]);
             }
         }
     }
@@ -307,7 +312,7 @@ __global__ __launch_bounds__(64) void band_l1_dpred_kernel(
     float sum = 0.f;
 #pragma unroll 8
     for (int x = 0; x < 64; ++x) sum = sum + red[lane * BC_PITCH + x];
-    const float k = scale * (row_scale ? row_scale[b] : 1.f);
+    const float k = Kind::factor(scale, row_scale ? row_scale[b] : 1.f);
     if (stored) *out = oi < n ? sum * k : 0.f;
 }
 
@@ -318,6 +323,41 @@ static int bc_check(int B, int C, int N, int M, float scale, int bandwidth) {
     if (bandwidth < 0) return fail(ALIGNER_EINVAL, "bandwidth must be at least 0");
     if (C > BD_MAX_C) return fail(ALIGNER_EDOM, "C=%d too large (<= %d)", C, BD_MAX_C);
     return dtw_band_domain(B, N, bandwidth);
+}
+
+template <class Kind>
+static int bc_forward(const float *pred, const float *target, const int32_t *n_dev, const int32_t *m_dev, int bandwidth,
+                      float scale, float *cost_band_out, int B, int C, int N, int M, void *stream) {
+    if (!pred || !target || !cost_band_out) return fail(ALIGNER_EINVAL, "null pointer");
+    if (const int rc = bc_check(B, C, N, M, scale, bandwidth)) return rc;
+    const int W = 2 * bandwidth + 1, nch = (W + BC_RB - 1 + 63) / 64, nrb = (N + BC_RB - 1) / BC_RB;
+    hipLaunchKernelGGL(bc_cost_kernel<Kind>, dim3((unsigned)(nch * nrb + 3) / 4, 1, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       pred, target, n_dev, m_dev, bandwidth, scale, cost_band_out, C, N, M, nch);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+
+template <class Kind>
+static int bc_backward(const float *grad_band, const float *pred, const float *target, const int32_t *n_dev,
+                       const int32_t *m_dev, int bandwidth, float scale, const float *row_scale,
+                       float *dpred_out, float *dtarget_out, int B, int C, int N, int M, void *stream) {
+    static_assert(Kind::has_backward, "this kind has no gradient");
+    if (!grad_band || !pred || !target) return fail(ALIGNER_EINVAL, "null pointer");
+    if (!dpred_out && !dtarget_out) return fail(ALIGNER_EINVAL, "null pointer: no output");
+    if (const int rc = bc_check(B, C, N, M, scale, bandwidth)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nchunks = (C + BC_CC - 1) / BC_CC;
+    if (dpred_out) {
+        hipLaunchKernelGGL(bc_dpred_kernel<Kind>, dim3((N + BC_PR - 1) / BC_PR, nchunks, B), dim3(64), 0, s,
+                           grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dpred_out, C, N, M);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    if (dtarget_out) {
+        hipLaunchKernelGGL(bc_dtarget_kernel<Kind>, dim3((M + 63) / 64, (nchunks + 3) / 4, B), dim3(256), 0, s,
+                           grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dtarget_out, C, N, M);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    return ALIGNER_OK;
 }
 
 }  // namespace aligner
@@ -364,34 +404,27 @@ int aligner_soft_dtw_banded_f32(const float *cost_band, const int32_t *n_dev, co
 
 int aligner_l1_cost_banded_f32(const float *pred, const float *target, const int32_t *n_dev, const int32_t *m_dev, int bandwidth,
                                float scale, float *cost_band_out, int B, int C, int N, int M, void *stream) {
-    if (!pred || !target || !cost_band_out) return fail(ALIGNER_EINVAL, "null pointer");
-    if (const int rc = bc_check(B, C, N, M, scale, bandwidth)) return rc;
-    const int W = 2 * bandwidth + 1, nch = (W + BC_RB - 1 + 63) / 64, nrb = (N + BC_RB - 1) / BC_RB;
-    hipLaunchKernelGGL(band_l1_cost_kernel, dim3((unsigned)(nch * nrb + 3) / 4, 1, B), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       pred, target, n_dev, m_dev, bandwidth, scale, cost_band_out, C, N, M, nch);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    return ALIGNER_OK;
+    return bc_forward<CostL1>(pred, target, n_dev, m_dev, bandwidth, scale, cost_band_out, B, C, N, M, stream);
 }
 
 int aligner_l1_cost_banded_backward_f32(const float *grad_band, const float *pred, const float *target, const int32_t *n_dev,
                                         const int32_t *m_dev, int bandwidth, float scale, const float *row_scale,
                                         float *dpred_out, float *dtarget_out, int B, int C, int N, int M, void *stream) {
-    if (!grad_band || !pred || !target) return fail(ALIGNER_EINVAL, "null pointer");
-    if (!dpred_out && !dtarget_out) return fail(ALIGNER_EINVAL, "null pointer: no output");
-    if (const int rc = bc_check(B, C, N, M, scale, bandwidth)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nchunks = (C + BC_CC - 1) / BC_CC;
-    if (dpred_out) {
-        hipLaunchKernelGGL(band_l1_dpred_kernel, dim3((N + BC_PR - 1) / BC_PR, nchunks, B), dim3(64), 0, s,
-                           grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dpred_out, C, N, M);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
-    if (dtarget_out) {
-        hipLaunchKernelGGL(band_l1_dtarget_kernel, dim3((M + 63) / 64, (nchunks + 3) / 4, B), dim3(256), 0, s,
-                           grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dtarget_out, C, N, M);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
-    return ALIGNER_OK;
+    return bc_backward<CostL1>(grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dpred_out, dtarget_out,
+                               B, C, N, M, stream);
+}
+
+int aligner_l2_cost_banded_f32(const float *pred, const float *target, const int32_t *n_dev, const int32_t *m_dev, int bandwidth,
+                               float scale, int squared, float *cost_band_out, int B, int C, int N, int M, void *stream) {
+    if (squared) return bc_forward<CostL2>(pred, target, n_dev, m_dev, bandwidth, scale, cost_band_out, B, C, N, M, stream);
+    return bc_forward<CostL2Root>(pred, target, n_dev, m_dev, bandwidth, scale, cost_band_out, B, C, N, M, stream);
+}
+
+int aligner_l2_cost_banded_backward_f32(const float *grad_band, const float *pred, const float *target, const int32_t *n_dev,
+                                        const int32_t *m_dev, int bandwidth, float scale, const float *row_scale,
+                                        float *dpred_out, float *dtarget_out, int B, int C, int N, int M, void *stream) {
+    return bc_backward<CostL2>(grad_band, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dpred_out, dtarget_out,
+                               B, C, N, M, stream);
 }
 
 }  // extern "C"

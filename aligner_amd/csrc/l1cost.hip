@@ -14,8 +14,13 @@
 //                                             of the band and the 64 lanes' sums meet in LDS, added in lane order
 // k = scale g[b] is rounded once and multiplies the finished sum.  G is selected, never multiplied, by "the cell
 // exists", so whatever stands in G outside the cells reaches nothing.
+//
+// The kernels are written once over the cost kind (costkind.h): the same tiles, loads and order of summation give the
+// squared Euclidean cost sum_c (pred - target)^2 with its gradient 2 k sum G (pred - target), and the root of that
+// sum, which is forward only.
 #include "common.h"
 #include "device.h"
+#include "costkind.h"
 
 namespace aligner {
 
@@ -29,16 +34,12 @@ constexpr int LC_PITCH = 65;                // odd: the 64 lanes of the reductio
 constexpr int LC_MAX_C = 4096;
 constexpr int LC_NO_BAND = 1 << 30;
 
-// G[i,j] pushed through sign(p - t): G, -G or 0 (0 for a tie, and for a NaN, which compares false both ways)
-__device__ __forceinline__ float lc_signed(float p, float t, float g) {
-    return p > t ? g : (p < t ? -g : 0.f);
-}
-
 __device__ __forceinline__ float lc_lane(float v, int l) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
 
-__global__ __launch_bounds__(64 * LC_WAVES) void l1_cost_kernel(
+template <class Kind>
+__global__ __launch_bounds__(64 * LC_WAVES) void lc_cost_kernel(
         const float *__restrict__ pred, const float *__restrict__ target, const int *__restrict__ ns,
         const int *__restrict__ ms, int band, float scale, float *__restrict__ cost, int C, int N, int M, int nct) {
     const int lane = threadIdx.x & 63;
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void l1_cost_kernel(
                     if (c + k >= C) break;
                     const float *pk = p + (size_t)(c + k) * N;
 #pragma unroll
-                    for (int r = 0; r < LC_RB; ++r) acc[r] = acc[r] + __builtin_fabsf(tc[k] - pk[r]);
+                    for (int r = 0; r < LC_RB; ++r) acc[r] = Kind::term(tc[k], pk[r], acc[r]);
                 }
             }
         } else {                                                          // the last row block: rows past N repeat row N - 1
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void l1_cost_kernel(
             for (int c = 0; c < C; ++c, t += M, p += N) {
                 const float tv = *t, pl = p[rl];
 #pragma unroll
-                for (int r = 0; r < LC_RB; ++r) acc[r] = acc[r] + __builtin_fabsf(tv - lc_lane(pl, r));
+                for (int r = 0; r < LC_RB; ++r) acc[r] = Kind::term(tv, lc_lane(pl, r), acc[r]);
             }
         }
     }
@@ -104,13 +105,14 @@ __global__ __launch_bounds__(64 * LC_WAVES) void l1_cost_kernel(
         const int i = i0 + r;
         if (i >= N) break;
         const int dist = i > j ? i - j : j - i;
-        float v = dist <= band ? acc[r] * scale : __builtin_huge_valf();
+        float v = dist <= band ? Kind::finish(acc[r], scale) : __builtin_huge_valf();
         v = (i < n && j < m) ? v : 0.f;
         out[(size_t)r * M] = v;
     }
 }
 
-__global__ __launch_bounds__(64 * LC_WAVES) void l1_cost_dtarget_kernel(
+template <class Kind>
+__global__ __launch_bounds__(64 * LC_WAVES) void lc_dtarget_kernel(
         const float *__restrict__ G, const float *__restrict__ pred, const float *__restrict__ target,
         const int *__restrict__ ns, const int *__restrict__ ms, int band, float scale, const float *__restrict__ row_scale,
         float *__restrict__ dtarget, int C, int N, int M) {
@@ -150,25 +152,25 @@ __global__ __launch_bounds__(64 * LC_WAVES) void l1_cost_dtarget_kernel(
 #pragma unroll
             for (int r = 0; r < LC_TR; ++r) gv[r] = gn[r];
             load_g(ib + LC_TR, gn);
-            if (ib + LC_TR <= N && cmax == LC_CC - 1) {
+            if (ib + LC_TR <= ihi && cmax == LC_CC - 1) {                  // (all LC_TR rows inside the utterance)
 #pragma unroll
                 for (int cc = 0; cc < LC_CC; ++cc)
 #pragma unroll
                     for (int r = 0; r < LC_TR; ++r)
-                        acc[cc] = acc[cc] + lc_signed(p[(size_t)cc * N + ib + r], tv[cc], gv[r]);
+                        acc[cc] = Kind::back(p[(size_t)cc * N + ib + r], tv[cc], gv[r], acc[cc]);
             } else {                                                      // the last rows or channels: repeat the last one
-                const int rl = ib + lane < N ? ib + lane : N - 1;
+                const int rl = ib + lane < ihi ? ib + lane : ihi - 1;     // (a row of the utterance: costkind.h)
 #pragma unroll
                 for (int cc = 0; cc < LC_CC; ++cc) {
                     const float pl = p[(size_t)(cc < cmax ? cc : cmax) * N + rl];
 #pragma unroll
-                    for (int r = 0; r < LC_TR; ++r) acc[cc] = acc[cc] + lc_signed(lc_lane(pl, r), tv[cc], gv[r]);
+                    for (int r = 0; r < LC_TR; ++r) acc[cc] = Kind::back(lc_lane(pl, r), tv[cc], gv[r], acc[cc]);
                 }
             }
         }
     }
     if (j >= M) return;
-    const float k = -(scale * (row_scale ? row_scale[b] : 1.f));
+    const float k = -Kind::factor(scale, row_scale ? row_scale[b] : 1.f);
     float *out = dtarget + ((size_t)b * C + c0) * M + j;
 #pragma unroll
     for (int cc = 0; cc < LC_CC; ++cc)
@@ -176,7 +178,8 @@ __global__ __launch_bounds__(64 * LC_WAVES) void l1_cost_dtarget_kernel(
 }
 
 // (three waves a SIMD, 168 VGPRs: left to itself the compiler takes 229 for the loads a step ahead, and two waves)
-__global__ __launch_bounds__(64, 3) void l1_cost_dpred_kernel(
+template <class Kind>
+__global__ __launch_bounds__(64, 3) void lc_dpred_kernel(
         const float *__restrict__ G, const float *__restrict__ pred, const float *__restrict__ target,
         const int *__restrict__ ns, const int *__restrict__ ms, int band, float scale, const float *__restrict__ row_scale,
         float *__restrict__ dpred, int C, int N, int M) {
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(64, 3) void l1_cost_dpred_kernel(
     // target and G of columns jt .. jt + 63 (G from a cell inside the tensor, then masked), a step ahead of their use
     auto load_tile = [&](int jt, float (&tout)[LC_CC], float (&gout)[LC_PR]) {
         const int j = jt + lane;
-        const int jc = j < M ? j : M - 1;
+        const int jc = j < jhi ? j : jhi - 1;                             // (a column of the utterance: costkind.h)
 #pragma unroll
         for (int cc = 0; cc < LC_CC; ++cc) tout[cc] = tb[(size_t)(cc < cmax ? cc : cmax) * M + jc];
 #pragma unroll
@@ -239,7 +242,7 @@ __global__ __launch_bounds__(64, 3) void l1_cost_dpred_kernel(
 #pragma unroll
         for (int cc = 0; cc < LC_CC; ++cc)
 #pragma unroll
-            for (int r = 0; r < LC_PR; ++r) acc[cc][r] = acc[cc][r] + lc_signed(pv[cc][r], tv[cc], gv[r]);
+            for (int r = 0; r < LC_PR; ++r) acc[cc][r] = Kind::back(pv[cc][r], tv[cc], gv[r], acc[cc][r]);
     }
     // sum number q = cc LC_PR + r of every lane to lane q, added in lane order
 #pragma unroll
@@ -250,7 +253,7 @@ __global__ __launch_bounds__(64, 3) void l1_cost_dpred_kernel(
     float sum = 0.f;
 #pragma unroll 8
     for (int x = 0; x < 64; ++x) sum = sum + red[lane * LC_PITCH + x];
-    const float k = scale * (row_scale ? row_scale[b] : 1.f);
+    const float k = Kind::factor(scale, row_scale ? row_scale[b] : 1.f);
     if (stored) *out = oi < n ? sum * k : 0.f;
 }
 
@@ -266,6 +269,41 @@ static int lc_check(int B, int C, int N, int M, float scale, int bandwidth) {
 }
 static int lc_band(int bandwidth) { return (bandwidth < 0 || bandwidth > LC_NO_BAND) ? LC_NO_BAND : bandwidth; }
 
+template <class Kind>
+static int lc_forward(const float *pred, const float *target, const int32_t *n_dev, const int32_t *m_dev, int bandwidth,
+                      float scale, float *cost_out, int B, int C, int N, int M, void *stream) {
+    if (!pred || !target || !cost_out) return fail(ALIGNER_EINVAL, "null pointer");
+    if (const int rc = lc_check(B, C, N, M, scale, bandwidth)) return rc;
+    const int nct = (M + 63) / 64, nrb = (N + LC_RB * LC_WAVES - 1) / (LC_RB * LC_WAVES);      // nct nrb <= N M / 64 + N + M
+    hipLaunchKernelGGL(lc_cost_kernel<Kind>, dim3((unsigned)nct * nrb, 1, B), dim3(64 * LC_WAVES), 0, static_cast<hipStream_t>(stream),
+                       pred, target, n_dev, m_dev, lc_band(bandwidth), scale, cost_out, C, N, M, nct);
+    ALIGNER_HIP_CHECK(hipGetLastError());
+    return ALIGNER_OK;
+}
+
+template <class Kind>
+static int lc_backward(const float *grad_cost, const float *pred, const float *target, const int32_t *n_dev,
+                       const int32_t *m_dev, int bandwidth, float scale, const float *row_scale,
+                       float *dpred_out, float *dtarget_out, int B, int C, int N, int M, void *stream) {
+    static_assert(Kind::has_backward, "this kind has no gradient");
+    if (!grad_cost || !pred || !target) return fail(ALIGNER_EINVAL, "null pointer");
+    if (!dpred_out && !dtarget_out) return fail(ALIGNER_EINVAL, "null pointer: no output");
+    if (const int rc = lc_check(B, C, N, M, scale, bandwidth)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int band = lc_band(bandwidth), nchunks = (C + LC_CC - 1) / LC_CC;
+    if (dpred_out) {
+        hipLaunchKernelGGL(lc_dpred_kernel<Kind>, dim3((N + LC_PR - 1) / LC_PR, nchunks, B), dim3(64), 0, s,
+                           grad_cost, pred, target, n_dev, m_dev, band, scale, row_scale, dpred_out, C, N, M);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    if (dtarget_out) {
+        hipLaunchKernelGGL(lc_dtarget_kernel<Kind>, dim3((M + 63) / 64, (nchunks + LC_WAVES - 1) / LC_WAVES, B), dim3(64 * LC_WAVES), 0, s,
+                           grad_cost, pred, target, n_dev, m_dev, band, scale, row_scale, dtarget_out, C, N, M);
+        ALIGNER_HIP_CHECK(hipGetLastError());
+    }
+    return ALIGNER_OK;
+}
+
 }  // namespace aligner
 
 using namespace aligner;
@@ -274,34 +312,27 @@ extern "C" {
 
 int aligner_l1_cost_f32(const float *pred, const float *target, const int32_t *n_dev, const int32_t *m_dev, int bandwidth,
                         float scale, float *cost_out, int B, int C, int N, int M, void *stream) {
-    if (!pred || !target || !cost_out) return fail(ALIGNER_EINVAL, "null pointer");
-    if (const int rc = lc_check(B, C, N, M, scale, bandwidth)) return rc;
-    const int nct = (M + 63) / 64, nrb = (N + LC_RB * LC_WAVES - 1) / (LC_RB * LC_WAVES);      // nct nrb <= N M / 64 + N + M
-    hipLaunchKernelGGL(l1_cost_kernel, dim3((unsigned)nct * nrb, 1, B), dim3(64 * LC_WAVES), 0, static_cast<hipStream_t>(stream),
-                       pred, target, n_dev, m_dev, lc_band(bandwidth), scale, cost_out, C, N, M, nct);
-    ALIGNER_HIP_CHECK(hipGetLastError());
-    return ALIGNER_OK;
+    return lc_forward<CostL1>(pred, target, n_dev, m_dev, bandwidth, scale, cost_out, B, C, N, M, stream);
 }
 
 int aligner_l1_cost_backward_f32(const float *grad_cost, const float *pred, const float *target, const int32_t *n_dev,
                                  const int32_t *m_dev, int bandwidth, float scale, const float *row_scale,
                                  float *dpred_out, float *dtarget_out, int B, int C, int N, int M, void *stream) {
-    if (!grad_cost || !pred || !target) return fail(ALIGNER_EINVAL, "null pointer");
-    if (!dpred_out && !dtarget_out) return fail(ALIGNER_EINVAL, "null pointer: no output");
-    if (const int rc = lc_check(B, C, N, M, scale, bandwidth)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int band = lc_band(bandwidth), nchunks = (C + LC_CC - 1) / LC_CC;
-    if (dpred_out) {
-        hipLaunchKernelGGL(l1_cost_dpred_kernel, dim3((N + LC_PR - 1) / LC_PR, nchunks, B), dim3(64), 0, s,
-                           grad_cost, pred, target, n_dev, m_dev, band, scale, row_scale, dpred_out, C, N, M);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
-    if (dtarget_out) {
-        hipLaunchKernelGGL(l1_cost_dtarget_kernel, dim3((M + 63) / 64, (nchunks + LC_WAVES - 1) / LC_WAVES, B), dim3(64 * LC_WAVES), 0, s,
-                           grad_cost, pred, target, n_dev, m_dev, band, scale, row_scale, dtarget_out, C, N, M);
-        ALIGNER_HIP_CHECK(hipGetLastError());
-    }
-    return ALIGNER_OK;
+    return lc_backward<CostL1>(grad_cost, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dpred_out, dtarget_out,
+                               B, C, N, M, stream);
+}
+
+int aligner_l2_cost_f32(const float *pred, const float *target, const int32_t *n_dev, const int32_t *m_dev, int bandwidth,
+                        float scale, int squared, float *cost_out, int B, int C, int N, int M, void *stream) {
+    if (squared) return lc_forward<CostL2>(pred, target, n_dev, m_dev, bandwidth, scale, cost_out, B, C, N, M, stream);
+    return lc_forward<CostL2Root>(pred, target, n_dev, m_dev, bandwidth, scale, cost_out, B, C, N, M, stream);
+}
+
+int aligner_l2_cost_backward_f32(const float *grad_cost, const float *pred, const float *target, const int32_t *n_dev,
+                                 const int32_t *m_dev, int bandwidth, float scale, const float *row_scale,
+                                 float *dpred_out, float *dtarget_out, int B, int C, int N, int M, void *stream) {
+    return lc_backward<CostL2>(grad_cost, pred, target, n_dev, m_dev, bandwidth, scale, row_scale, dpred_out, dtarget_out,
+                               B, C, N, M, stream);
 }
 
 }  // extern "C"

@@ -139,7 +139,8 @@ def dtw_path_l1(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tens
             l1 = (pred[b][:, ij[:, 0]] - target[b][:, ij[:, 1]]).abs().mean()      # mean L1 distance along the path
         # on a cost tensor of one's own: cost[b, ij[:, 0], ij[:, 1]].sum() + p * (stalls) is value[b]
 
-    or index any other pair of features (mel cepstra for MCD-DTW) with the same pairs and average."""
+    or index any other pair of features with the same pairs and average.  For MCD-DTW, which aligns under the Euclidean
+    distance of the mel cepstra themselves, mcd_dtw() (l2cost.py) is the call."""
     banded = bandwidth is not None and 0 <= int(bandwidth) <= 127
     if banded:
         cost = l1_cost_banded(pred, target, n, m, int(bandwidth), scale)

@@ -35,14 +35,13 @@ def _checked(pred, target, bandwidth, scale, also=()) -> Tuple[int, int, int, in
     return B, C, N, target.shape[2], -1 if bandwidth is None else min(int(bandwidth), 2 ** 30), scale, dev
 
 
-def l1_cost(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None,
-            bandwidth: Optional[int] = None, scale: float = 1.0) -> torch.Tensor:
-    """cost [B,N,M] of the module text, fp32; every cell is written.
+# The kinds of the cost: L1, and the two Euclidean ones of l2cost.py.  The wrappers of both modules are these helpers
+# with the kind fixed.
+L1, L2, L2_ROOT = "l1", "l2", "l2root"
 
-    pred [B,C,N], target [B,C,M]: GPU tensors (bf16 / fp16 are cast to fp32, non-contiguous ones copied); n / m [B]: the
-    utterances' lengths (None: N / M; larger values are clamped).  B <= 65535, C <= 4096, N*M < 2^29 (an AlignerError of
-    code EDOM beyond).  Not attached to autograd (soft_dtw_l1_loss() is).  Empty shapes return without a launch.
-    Asynchronous on the current stream."""
+
+def _cost(kind, pred, target, n, m, bandwidth, scale) -> torch.Tensor:
+    """l1_cost() / l2_cost(): the [B,N,M] table of `kind`."""
     B, C, N, M, band, scale, dev = _checked(pred, target, bandwidth, scale)
     nn = lengths(n, B, dev, "n")
     mm = lengths(m, B, dev, "m")
@@ -53,20 +52,31 @@ def l1_cost(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] 
     p, t = f32c(pred), f32c(target)
     cost = torch.empty((B, N, M), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.aligner_l1_cost_f32(p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), band, scale, cost.data_ptr(),
-                                           B, C, N, M, stream(dev)))
+        if kind == L1:
+            rc = lib.aligner_l1_cost_f32(p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), band, scale, cost.data_ptr(),
+                                         B, C, N, M, stream(dev))
+        else:
+            rc = lib.aligner_l2_cost_f32(p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), band, scale, int(kind == L2),
+                                         cost.data_ptr(), B, C, N, M, stream(dev))
+        _lib.check(rc)
     return cost
 
 
-def l1_cost_backward(grad_cost: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None,
-                     m: Optional[torch.Tensor] = None, bandwidth: Optional[int] = None, scale: float = 1.0,
-                     row_scale: Optional[torch.Tensor] = None, want: Tuple[bool, bool] = (True, True)
-                     ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """(dpred [B,C,N] or None, dtarget [B,C,M] or None) of the module text, fp32, with G = grad_cost [B,N,M].
+def l1_cost(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None,
+            bandwidth: Optional[int] = None, scale: float = 1.0) -> torch.Tensor:
+    """cost [B,N,M] of the module text, fp32; every cell is written.
 
-    row_scale [B]: the per-utterance factor g (None: 1), so that nobody scales G in a pass of its own.  G is never read
-    as a value where a cell does not exist.  One owner per output element and no atomics: the same bits on every call,
-    and each output has the same bits whether or not the other is asked for.  Domain and lengths as in l1_cost()."""
+    pred [B,C,N], target [B,C,M]: GPU tensors (bf16 / fp16 are cast to fp32, non-contiguous ones copied); n / m [B]: the
+    utterances' lengths (None: N / M; larger values are clamped).  B <= 65535, C <= 4096, N*M < 2^29 (an AlignerError of
+    code EDOM beyond).  Not attached to autograd (soft_dtw_l1_loss() is).  Empty shapes return without a launch.
+    Asynchronous on the current stream."""
+    return _cost(L1, pred, target, n, m, bandwidth, scale)
+
+
+def _cost_backward(kind, grad_cost, pred, target, n, m, bandwidth, scale, row_scale, want):
+    """l1_cost_backward() / l2_cost_backward(): (dpred, dtarget) of `kind` (L1 or L2)."""
+    if kind not in (L1, L2):
+        raise ValueError("the root of the Euclidean cost has no gradient: train on the squared cost")
     B, C, N, M, band, scale, dev = _checked(pred, target, bandwidth, scale, also=((grad_cost, "grad_cost"),))
     want_p, want_t = bool(want[0]), bool(want[1])
     nn = lengths(n, B, dev, "n")
@@ -88,36 +98,55 @@ def l1_cost_backward(grad_cost: torch.Tensor, pred: torch.Tensor, target: torch.
     lib = _lib.load()
     g, p, t = f32c(grad_cost), f32c(pred), f32c(target)
     with torch.cuda.device(dev):
-        _lib.check(lib.aligner_l1_cost_backward_f32(g.data_ptr(), p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), band, scale,
-                                                    ptr(rs), ptr(dpred), ptr(dtarget), B, C, N, M, stream(dev)))
+        fn = lib.aligner_l1_cost_backward_f32 if kind == L1 else lib.aligner_l2_cost_backward_f32
+        _lib.check(fn(g.data_ptr(), p.data_ptr(), t.data_ptr(), ptr(nn), ptr(mm), band, scale, ptr(rs), ptr(dpred), ptr(dtarget),
+                      B, C, N, M, stream(dev)))
     return dpred, dtarget
 
 
-class _SoftDtwL1Loss(torch.autograd.Function):
+def l1_cost_backward(grad_cost: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None,
+                     m: Optional[torch.Tensor] = None, bandwidth: Optional[int] = None, scale: float = 1.0,
+                     row_scale: Optional[torch.Tensor] = None, want: Tuple[bool, bool] = (True, True)
+                     ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(dpred [B,C,N] or None, dtarget [B,C,M] or None) of the module text, fp32, with G = grad_cost [B,N,M].
+
+    row_scale [B]: the per-utterance factor g (None: 1), so that nobody scales G in a pass of its own.  G is never read
+    as a value where a cell does not exist.  One owner per output element and no atomics: the same bits on every call,
+    and each output has the same bits whether or not the other is asked for.  Domain and lengths as in l1_cost()."""
+    return _cost_backward(L1, grad_cost, pred, target, n, m, bandwidth, scale, row_scale, want)
+
+
+class _SoftDtwCostLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, target, n, m, gamma, warp_penalty, bandwidth, scale):
-        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    def forward(ctx, kind, pred, target, n, m, gamma, warp_penalty, bandwidth, scale):
+        need = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         # the cost table lives for these two lines: the DP's backward reads R only, and E overwrites R in place
-        cost = l1_cost(pred, target, n, m, bandwidth, scale)
+        cost = _cost(kind, pred, target, n, m, bandwidth, scale)
         value, E = soft_dtw(cost, n, m, gamma, warp_penalty, bandwidth, want_grad=need)
         del cost
         if need:
             ctx.save_for_backward(pred, target, E)
         ctx.lengths = (n, m)
-        ctx.band, ctx.scale = bandwidth, scale
+        ctx.kind, ctx.band, ctx.scale = kind, bandwidth, scale
         return value
 
     @staticmethod
     def backward(ctx, g_value):
-        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        want = (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         if not (want[0] or want[1]) or g_value is None:
-            return (None,) * 8
+            return (None,) * 9
         pred, target, E = ctx.saved_tensors
         n, m = ctx.lengths
         # (an utterance without an alignment has E = 0 and with it zero gradients, whatever its g)
-        dpred, dtarget = l1_cost_backward(E, pred, target, n, m, ctx.band, ctx.scale, row_scale=g_value, want=want)
-        return (None if dpred is None else dpred.to(pred.dtype), None if dtarget is None else dtarget.to(target.dtype),
+        dpred, dtarget = _cost_backward(ctx.kind, E, pred, target, n, m, ctx.band, ctx.scale, g_value, want)
+        return (None, None if dpred is None else dpred.to(pred.dtype), None if dtarget is None else dtarget.to(target.dtype),
                 None, None, None, None, None, None)
+
+
+def _soft_dtw_cost_loss(kind, pred, target, n, m, gamma, warp_penalty, bandwidth, scale, reduction, zero_infinity):
+    check_reduction(reduction)
+    value = _SoftDtwCostLoss.apply(kind, pred, target, n, m, gamma, warp_penalty, bandwidth, scale)
+    return reduced(value, reduction, zero_infinity)
 
 
 def soft_dtw_l1_loss(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch.Tensor] = None,
@@ -129,5 +158,4 @@ def soft_dtw_l1_loss(pred: torch.Tensor, target: torch.Tensor, n: Optional[torch
     after the forward pass and no cdist graph is kept: what is saved is pred, target, E and the lengths.  Gradients come
     back in the inputs' dtypes, None for an input that does not require one.  reduction and zero_infinity as in
     soft_dtw_loss(); soft_dtw()'s domain (N <= 1024).  Parallel Tacotron 2: gamma 0.05, warp_penalty 128, bandwidth 60."""
-    check_reduction(reduction)
-    return reduced(_SoftDtwL1Loss.apply(pred, target, n, m, gamma, warp_penalty, bandwidth, scale), reduction, zero_infinity)
+    return _soft_dtw_cost_loss(L1, pred, target, n, m, gamma, warp_penalty, bandwidth, scale, reduction, zero_infinity)

@@ -50,7 +50,9 @@ extern "C" {
  *    banded L1 cost table with the gradient -- aligner_l1_cost_f32 / aligner_l1_cost_backward_f32; the three in band
  *    storage, O(N w) memory and any N -- aligner_soft_dtw_banded_f32 / aligner_l1_cost_banded_f32 /
  *    aligner_l1_cost_banded_backward_f32; and hard DTW, the minimum-cost warping path with its backtrack, in both
- *    storage forms -- aligner_dtw_path_f32 / aligner_dtw_path_banded_f32 and their *_workspace_bytes. */
+ *    storage forms -- aligner_dtw_path_f32 / aligner_dtw_path_banded_f32 and their *_workspace_bytes; and the
+ *    Euclidean cost tables, squared (with the gradient) and root, in both storage forms -- aligner_l2_cost_f32 /
+ *    aligner_l2_cost_backward_f32 / aligner_l2_cost_banded_f32 / aligner_l2_cost_banded_backward_f32. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -873,6 +875,41 @@ int aligner_l1_cost_banded_f32(const float *pred_dev, const float *target_dev, c
                                int bandwidth, float scale, float *cost_band_out_dev,
                                int B, int C, int N, int M, void *hip_stream);
 int aligner_l1_cost_banded_backward_f32(const float *grad_band_dev, const float *pred_dev, const float *target_dev,
+                                        const int32_t *n_dev, const int32_t *m_dev, int bandwidth, float scale,
+                                        const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
+                                        int B, int C, int N, int M, void *hip_stream);
+
+/*
+ * The Euclidean cost tables, dense and in band storage: the four L1 cost calls above with another cost in the cells.
+ * Build-defined.  Existing cells, fill values (+inf / 0 dense, 0 in band storage), lengths and their clamps, band,
+ * layouts, row_scale, domains, error codes and their order are those of the L1 call of the same storage form.
+ *
+ *     squared != 0:  cost[b,i,j] = scale      sum_c (pred[b,c,i] - target[b,c,j])^2        (Soft-DTW's own cost)
+ *     squared == 0:  cost[b,i,j] = scale sqrt(sum_c (pred[b,c,i] - target[b,c,j])^2)       (the distance MCD-DTW averages)
+ *
+ *     dpred[b,c,i]   =  k sum_j G[b,i,j] (pred[b,c,i] - target[b,c,j])      k = (2 scale) row_scale[b], rounded once
+ *     dtarget[b,c,j] = -k sum_i G[b,i,j] (pred[b,c,i] - target[b,c,j])      (row_scale null: k = 2 scale)
+ *
+ * The backward calls are those of the squared cost; the root has none (it needs the finished table and is singular at
+ * distance 0).  Per cell d = target - pred and acc = fma(d, d, acc) over the channels in order, the direct form on the
+ * vector ALU: the error is relative to the distance itself, not to the norms.  The dense and the band call run the
+ * same operations in the same order, so the band table has the dense table's bits on the cells that exist.  G is
+ * masked by "the cell exists" before it is multiplied, and pred rows / target columns are taken from inside the
+ * lengths: a NaN in G where no cell exists, or in pred / target past the lengths, reaches nothing.  pred and target
+ * inside the lengths must be such that their differences are finite.  No atomics, no workspace; the same bits on
+ * every call, and each gradient has the bits it has beside the other.
+ */
+int aligner_l2_cost_f32(const float *pred_dev, const float *target_dev, const int32_t *n_dev, const int32_t *m_dev,
+                        int bandwidth, float scale, int squared, float *cost_out_dev,
+                        int B, int C, int N, int M, void *hip_stream);
+int aligner_l2_cost_backward_f32(const float *grad_cost_dev, const float *pred_dev, const float *target_dev,
+                                 const int32_t *n_dev, const int32_t *m_dev, int bandwidth, float scale,
+                                 const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
+                                 int B, int C, int N, int M, void *hip_stream);
+int aligner_l2_cost_banded_f32(const float *pred_dev, const float *target_dev, const int32_t *n_dev, const int32_t *m_dev,
+                               int bandwidth, float scale, int squared, float *cost_band_out_dev,
+                               int B, int C, int N, int M, void *hip_stream);
+int aligner_l2_cost_banded_backward_f32(const float *grad_band_dev, const float *pred_dev, const float *target_dev,
                                         const int32_t *n_dev, const int32_t *m_dev, int bandwidth, float scale,
                                         const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
                                         int B, int C, int N, int M, void *hip_stream);
