@@ -1,7 +1,7 @@
 // Weight / bias gradient of the encoders' convolution (convgemm.hip) on MI355X (gfx950).
 //
 // For y = act(conv1d(x, w, b)) with "same" padding, K in {1, 3, 5}, act = ReLU or none:
-//   dYpre       = dY [y > 0]  (dY without an activation)
+//   dYpre       = 0 where y <= 0, dY elsewhere -- torch.relu's rule: a NaN y passes its cotangent  (dY without an activation)
 //   db[o]       = sum_{b,t} dYpre[b,o,t]
 //   dW[o,i,tap] = sum_{b,t} dYpre[b,o,t] x[b,i,t+tap-K/2]
 // A GEMM M = Cout, N = Cin K over the reduction index (b, t), both operands with t contiguous.  The input gradient is the
@@ -37,7 +37,7 @@ struct ConvBwdParams {
 
 __device__ __forceinline__ float cw_gy(const ConvBwdParams &p, size_t idx) {
     const float g = p.gy[idx];
-    return (p.relu && !(p.y[idx] > 0.f)) ? 0.f : g;
+    return (p.relu && p.y[idx] <= 0.f) ? 0.f : g;
 }
 
 // one chunk (utterance b, frames t0 .. t0 + 31) of both operands into registers: element j of a thread is
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void conv_bwd_w_kernel(ConvBwdParams p) {
 #pragma unroll
         for (int j = 0; j < CW_PER; ++j) {
             const int idx = tid + 256 * j, rl = idx >> 5, tt = idx & 31;
-            const float v = (p.relu && !(r.m[j] > 0.f)) ? 0.f : r.a[j];
+            const float v = (p.relu && r.m[j] <= 0.f) ? 0.f : r.a[j];
             As[rl * CW_P + tt] = v;
             Bs[rl * CW_P + tt] = r.bx[j];
             const int o = o0 + rl, t = t0 + tt;

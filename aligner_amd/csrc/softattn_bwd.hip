@@ -291,7 +291,7 @@ __global__ __launch_bounds__(SB_THREADS) void softattn_bwd_col_kernel(SaBwdParam
             const int c = 32 * ct + sb_row(e, half);
             if (c < p.C) {
                 float v = aq[ct][e];
-                if (p.l2) v = fmaf(-Qb[(size_t)c * p.Ty + col], dsum, v);
+                if (p.l2 && tx > 0) v = fmaf(-Qb[(size_t)c * p.Ty + col], dsum, v);   // t_x = 0: exactly 0, whatever q holds
                 p.dq[((size_t)b * p.C + c) * p.Ty + col] = f * v;
             }
         }

@@ -29,9 +29,16 @@ def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
     return f32c(t)
 
 
+def _chk_weight(w: torch.Tensor) -> None:
+    if not w.is_cuda:
+        raise ValueError("weight must be a GPU tensor")
+    if w.dim() != 3:
+        raise ValueError("weight must be [Cout,Cin,K]")
+
+
 _workspaces = _lib.StreamWorkspaces(zero=False)
 _conv_workspaces = _lib.StreamWorkspaces(zero=False)      # split activations of the wide conv layers
-_prepared: dict = {}          # (weight ptr, shape, device, stream) -> (version, prepared weights, weight)
+_prepared: dict = {}          # (weight ptr, dtype, shape, strides, device, stream) -> (version, prepared weights, weight)
 _prepared_t: dict = {}        # the same for the transposed weights (the input gradient's convolution)
 _bwd_workspaces = _lib.StreamWorkspaces(zero=False)       # the backward passes' column statistics / weight-gradient partials
 
@@ -40,27 +47,53 @@ def _workspace(device, nbytes: int) -> torch.Tensor:
     return _workspaces.get(device, nbytes)             # one per (device, stream)
 
 
-def _prepared_weights(weight: torch.Tensor, device) -> torch.Tensor:
-    """weights -> split bf16 halves in the matrix cores' fragment order (aligner_conv1d_prepare_f32, a few
-    microseconds), kept per weight tensor (and stream: no cross-stream ordering) until the tensor is modified in place
-    (torch's version counter: the entry is then re-prepared in place, so a training loop does not grow the cache) or
-    replaced.  Updates that bypass the counter (`p.data.copy_()`, writes through a storage alias) are NOT seen: call
-    invalidate_prepared() after such an update."""
+def _prepared_image(table: dict, weight: torch.Tensor, device, transposed: bool, fresh: bool = False) -> torch.Tensor:
+    """The prepared image of `weight` (or of its transpose) from `table`, written when it is missing or stale.
+
+    An entry belongs to the CALLER's tensor: the key is its address, dtype, shape, strides, device and the current stream
+    (no cross-stream ordering), the entry records torch's version counter and holds the tensor, so its address is not
+    reused while the entry lives.  A weight the kernels cannot read as it is (bf16, a non-contiguous view) is converted for
+    the prepare launch alone, once per update: the fp32 copy is dropped again, the cache never sees it.  In-place updates
+    (optimizers, `p.sub_()`, through a view or `detach()` alias: one shared counter) move the counter and the image is
+    re-prepared into the same buffer, so a training loop does not grow the cache.  Updates that bypass the counter
+    (`p.data.copy_()`, EMA through `.data`) are NOT seen: call invalidate_prepared() after them.
+
+    Fused optimizers (`Adam(fused=True)`, `SGD(fused=True)`, ...) update the parameters WITHOUT moving the counter, so the
+    image of a weight that is being trained is never trusted: with `fresh` (the autograd path, when the weight gets a
+    gradient) or `weight.requires_grad` the image is prepared again on every call, into the entry's buffer.  Only an alias
+    of such a parameter that does not require grad itself (`p.detach()`) still needs invalidate_prepared() after a fused step.
+
+    While the stream is capturing, the cache is neither read nor written: the image is prepared into a buffer allocated
+    inside the capture, so the graph owns its prepare launch and its image, and every replay reads the weights as they are
+    then (a cached image would freeze the weights of capture time into the graph, and could be evicted under it)."""
     lib = _lib.load()
     Cout, Cin, K = weight.shape
-    key = (weight.data_ptr(), Cout, Cin, K, device, stream(device))
-    ent = _prepared.get(key)
-    if ent is None or ent[0] != weight._version:
-        nprep = lib.aligner_conv1d_prepared_bytes(Cout, Cin, K)
-        if nprep == 0:
-            raise ValueError(f"kernel size {K} not supported (1, 3, 5)")
-        prep = ent[1] if ent is not None else torch.empty(nprep, dtype=torch.uint8, device=device)
-        _lib.check(lib.aligner_conv1d_prepare_f32(weight.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K, stream(device)))
-        if ent is None and len(_prepared) >= 256:
-            _prepared.pop(next(iter(_prepared)))       # oldest entry only
-        _prepared[key] = (weight._version, prep, weight)   # holding `weight` keeps its address from being reused
+    nprep = lib.aligner_conv1d_prepared_bytes(Cin, Cout, K) if transposed else lib.aligner_conv1d_prepared_bytes(Cout, Cin, K)
+    if nprep == 0:
+        raise ValueError(f"kernel size {K} not supported (1, 3, 5)")
+    prepare = lib.aligner_conv1d_prepare_transposed_f32 if transposed else lib.aligner_conv1d_prepare_f32
+    if torch.cuda.is_current_stream_capturing():
+        prep = torch.empty(nprep, dtype=torch.uint8, device=device)
+        wf = f32c(weight)
+        _lib.check(prepare(wf.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K, stream(device)))
         return prep
-    return ent[1]
+    key = (weight.data_ptr(), weight.dtype, tuple(weight.shape), tuple(weight.stride()), device, stream(device))
+    ent = table.get(key)
+    if ent is not None and ent[0] == weight._version and not (fresh or weight.requires_grad):
+        return ent[1]
+    prep = ent[1] if ent is not None else torch.empty(nprep, dtype=torch.uint8, device=device)
+    wf = f32c(weight)                                  # a copy only for bf16 / strided weights, dropped on return
+    _lib.check(prepare(wf.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K, stream(device)))
+    if ent is None and len(table) >= 256:
+        table.pop(next(iter(table)))                   # oldest entry only
+    table[key] = (weight._version, prep, weight)
+    return prep
+
+
+def _prepared_weights(weight: torch.Tensor, device, fresh: bool = False) -> torch.Tensor:
+    """weights -> split bf16 halves in the matrix cores' fragment order (aligner_conv1d_prepare_f32, a few
+    microseconds), cached per weight tensor: _prepared_image()."""
+    return _prepared_image(_prepared, weight, device, False, fresh)
 
 
 def _needs_grad(*tensors) -> bool:
@@ -75,9 +108,9 @@ def conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     return _conv1d(x, weight, bias, relu)
 
 
-def _conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], relu: bool) -> torch.Tensor:
+def _conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], relu: bool, fresh: bool = False) -> torch.Tensor:
     _lib.require_gpu()
-    x = _chk(x, "x"); weight = _chk(weight, "weight")
+    x = _chk(x, "x"); _chk_weight(weight)              # the weight stays the caller's tensor: the cache is keyed on it
     bias = _chk(bias, "bias") if bias is not None else None
     B, Cin, T = x.shape
     Cout, Cin2, K = weight.shape
@@ -86,7 +119,7 @@ def _conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
     y = torch.empty((B, Cout, T), dtype=torch.float32, device=x.device)
     lib = _lib.load()
     with torch.cuda.device(x.device):
-        prep = _prepared_weights(weight, x.device)
+        prep = _prepared_weights(weight, x.device, fresh)
         # wide layers split their activations into a workspace first (csrc/convgemm.hip); narrow ones need none
         nws = lib.aligner_conv1d_workspace_bytes(B, Cin, Cout, T, K)
         ws = _conv_workspaces.get(x.device, nws) if nws else None
@@ -96,37 +129,24 @@ def _conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
     return y
 
 
-def _prepared_weights_transposed(weight: torch.Tensor, device) -> torch.Tensor:
+def _prepared_weights_transposed(weight: torch.Tensor, device, fresh: bool = False) -> torch.Tensor:
     """The prepared image of w'[i,o,k] = w[o,i,K-1-k] (aligner_conv1d_prepare_transposed_f32): the input gradient of the
     layer is the forward convolution of its output gradient with it.  Cached like _prepared_weights(), in a table of its
-    own, re-prepared when the weight's version counter moves."""
-    lib = _lib.load()
-    Cout, Cin, K = weight.shape
-    key = (weight.data_ptr(), Cout, Cin, K, device, stream(device))
-    ent = _prepared_t.get(key)
-    if ent is None or ent[0] != weight._version:
-        nprep = lib.aligner_conv1d_prepared_bytes(Cin, Cout, K)
-        if nprep == 0:
-            raise ValueError(f"kernel size {K} not supported (1, 3, 5)")
-        prep = ent[1] if ent is not None else torch.empty(nprep, dtype=torch.uint8, device=device)
-        _lib.check(lib.aligner_conv1d_prepare_transposed_f32(weight.data_ptr(), prep.data_ptr(), nprep, Cout, Cin, K,
-                                                             stream(device)))
-        if ent is None and len(_prepared_t) >= 256:
-            _prepared_t.pop(next(iter(_prepared_t)))
-        _prepared_t[key] = (weight._version, prep, weight)
-        return prep
-    return ent[1]
+    own."""
+    return _prepared_image(_prepared_t, weight, device, True, fresh)
 
 
 def conv1d_backward(x: torch.Tensor, weight: torch.Tensor, y: Optional[torch.Tensor], grad_y: torch.Tensor, relu: bool,
-                    need_x: bool = True, need_w: bool = True, need_b: bool = True
+                    need_x: bool = True, need_w: bool = True, need_b: bool = True, _fresh: bool = False
                     ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
     """Gradients of y = act(conv1d(x, weight, bias)) (act = ReLU when relu) given grad_y = dL/dy: (grad_x [B,Cin,T],
     grad_w [Cout,Cin,K], grad_b [Cout]), fp32, None where not asked for.  y (the layer's output) is needed with relu only.
+    The ReLU mask is torch.relu's: the cotangent is 0 where y <= 0 and passes elsewhere, so a NaN y passes it (a NaN
+    cotangent at a NaN activation reaches grad_w / grad_b, where a gradient scaler's overflow check looks for it).
     grad_w / grad_b: aligner_conv1d_backward_weight_f32; grad_x: the forward convolution of the masked grad_y with the
     transposed weights (aligner_conv1d_prepare_transposed_f32 + aligner_conv1d_prepared_ws_f32)."""
     _lib.require_gpu()
-    x = _chk(x, "x"); weight = _chk(weight, "weight"); gy = _chk(grad_y, "grad_y")
+    x = _chk(x, "x"); _chk_weight(weight); gy = _chk(grad_y, "grad_y")
     B, Cin, T = x.shape
     Cout, Cin2, K = weight.shape
     if Cin2 != Cin or tuple(gy.shape) != (B, Cout, T):
@@ -155,7 +175,7 @@ def conv1d_backward(x: torch.Tensor, weight: torch.Tensor, y: Optional[torch.Ten
                 x.data_ptr(), y.data_ptr() if relu else None, gy.data_ptr(), gyp.data_ptr() if (relu and need_x) else None,
                 ptr(gw), ptr(gb), ptr(ws), 0 if ws is None else ws.numel(), B, Cin, Cout, T, K, int(relu), stream(dev)))
         if need_x:
-            prep = _prepared_weights_transposed(weight, dev)
+            prep = _prepared_weights_transposed(weight, dev, _fresh)
             gx = torch.empty((B, Cin, T), dtype=torch.float32, device=dev)
             nws = lib.aligner_conv1d_workspace_bytes(B, Cout, Cin, T, K)
             ws = _conv_workspaces.get(dev, nws) if nws else None
@@ -168,11 +188,11 @@ class _Conv1d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
         ctx.set_materialize_grads(False)
-        xf, wf = _chk(x, "x"), _chk(weight, "weight")
-        y = _conv1d(xf, wf, bias, relu)
+        xf = _chk(x, "x")
+        y = _conv1d(xf, weight, bias, relu, fresh=ctx.needs_input_grad[1])     # a weight in training: never a cached image
         ctx.relu = relu
         ctx.dtypes = (x.dtype, weight.dtype, None if bias is None else bias.dtype)
-        ctx.save_for_backward(xf, wf, y if relu else None)
+        ctx.save_for_backward(xf, weight, y if relu else None)
         return y
 
     @staticmethod
@@ -181,7 +201,7 @@ class _Conv1d(torch.autograd.Function):
             return None, None, None, None
         x, w, y = ctx.saved_tensors
         nx, nw, nb = ctx.needs_input_grad[:3]
-        gx, gw, gb = conv1d_backward(x, w, y, gy, ctx.relu, need_x=nx, need_w=nw, need_b=nb)
+        gx, gw, gb = conv1d_backward(x, w, y, gy, ctx.relu, need_x=nx, need_w=nw, need_b=nb, _fresh=nw)
         dx, dw, db = ctx.dtypes
         return (None if gx is None else gx.to(dx), None if gw is None else gw.to(dw), None if gb is None else gb.to(db), None)
 
@@ -390,7 +410,7 @@ def encode(x: torch.Tensor, stack: List[Tuple[torch.Tensor, torch.Tensor]]) -> t
     c = Cin
     with torch.cuda.device(dev):
         for n, (w, b) in enumerate(stack):
-            w = _chk(w, "weight")
+            _chk_weight(w)
             b = _chk(b, "bias") if b is not None else None
             if w.shape[1] != c:
                 raise ValueError("channel mismatch")

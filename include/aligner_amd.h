@@ -563,7 +563,8 @@ int aligner_conv_stack_f32(const float *x_dev, const aligner_conv_layer *layers,
 
 /*
  * Backward of y = act(conv1d(x, w, b)) (act: ReLU when relu = 1, none when 0):
- *   dYpre = dY [y > 0] (dY when relu = 0), db[o] = sum_{b,t} dYpre[b,o,t], dW[o,i,k] = sum_{b,t} dYpre[b,o,t] x[b,i,t+k-K/2]
+ *   dYpre = 0 where y <= 0, dY elsewhere (torch.relu's rule: y = +0, -0 and y < 0 mask, a NaN y passes its cotangent;
+ *   dY when relu = 0), db[o] = sum_{b,t} dYpre[b,o,t], dW[o,i,k] = sum_{b,t} dYpre[b,o,t] x[b,i,t+k-K/2]
  *   dX = conv1d(dYpre, w') with w'[i,o,k] = w[o,i,K-1-k]: aligner_conv1d_prepare_transposed_f32 writes the prepared image
  *   of w' straight from w [Cout,Cin,K] (aligner_conv1d_prepared_bytes(Cin, Cout, K) bytes), then
  *   aligner_conv1d_prepared_ws_f32(dYpre, image, NULL bias, dX, ..., Cin = Cout, Cout = Cin, K, relu = 0).

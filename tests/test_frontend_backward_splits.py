@@ -88,12 +88,12 @@ def test_split_cases_cover_the_chunk_loop(built_lib):
 
 def _ref_conv_backward(x, w, y, gy, relu):
     """(dYpre, dX, dW, db) of y = act(conv1d(x, w, b, padding=K//2)) in float64 on x's device; the ReLU mask is the
-    kernel's rule, dY where y > 0 (so y = +0, -0 and y < 0 all mask)."""
+    kernel's rule, torch.relu's: 0 where y <= 0 (y = +0, -0 and y < 0 all mask), dY elsewhere (a NaN y passes it)."""
     x, w, gy = x.double(), w.double(), gy.double()
     B, Ci, T = x.shape
     Co, _, K = w.shape
     hk = K // 2
-    gyp = torch.where(y > 0, gy, torch.zeros_like(gy)) if relu else gy
+    gyp = torch.where(y <= 0, torch.zeros_like(gy), gy) if relu else gy
     xp = F.pad(x, (hk, hk))
     gp = F.pad(gyp, (hk, hk))
     a = gyp.permute(1, 0, 2).reshape(Co, B * T)

@@ -1,9 +1,12 @@
 """hipEvent times of the front end's backward entry points: aligner_softattn_backward_f32 at the bench shape
 [64,80,200,1000] (and a few others), and the conv backward (aligner_conv1d_backward_weight_f32, the transposed-weight dX
-convolution) at the C3 encoder layers beside the forward convolution of the same layer.  Prints achieved bytes/s against
-the compulsory traffic of each call.
+convolution) at the five encoder layers of tests/test_frontend_backward_splits.py FULL_CASES beside the forward convolution
+of the same layer, and the two prepare launches of the layer's weight images (what a call pays when its image is not
+cached: a weight in training, a captured graph).  Prints achieved bytes/s against the compulsory traffic of each call.
 
-    python tools/frontend_backward_time.py [--iters N]
+    python tools/frontend_backward_time.py [--iters N] [--conv-only]
+
+ALIGNER_AMD_LIB=<path to another build's libaligner_amd.so> times that build with the same script.
 """
 import argparse
 import os
@@ -31,14 +34,15 @@ def ev(fn, it, warm=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--conv-only", action="store_true")
     a = ap.parse_args()
     lib = _lib.load()
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device="cpu").manual_seed(0)
     print("soft-attention backward (grad_logp only, no prior; dK and dQ)")
-    for (B, C, Tx, Ty, sim) in [(64, 80, 200, 1000, "l2"), (64, 80, 200, 1000, "dot"), (16, 128, 224, 1000, "l2"),
-                                (8, 80, 500, 2000, "l2")]:
+    for (B, C, Tx, Ty, sim) in [] if a.conv_only else [(64, 80, 200, 1000, "l2"), (64, 80, 200, 1000, "dot"),
+                                                       (16, 128, 224, 1000, "l2"), (8, 80, 500, 2000, "l2")]:
         k = (torch.randn(B, C, Tx, generator=g) * 2).to(dev)
         q = (torch.randn(B, C, Ty, generator=g) * 2).to(dev)
         gl = torch.randn(B, Tx, Ty, generator=g).to(dev)
@@ -57,11 +61,12 @@ def main():
         print(f"  [{B},{C},{Tx},{Ty}] {sim}: {t:.1f} us ({nbytes / t / 1e6:.2f} TB/s on {nbytes / 1e6:.1f} MB); "
               f"dQ only (column kernel) {tq:.1f} us, dK kernel {t - tq:.1f} us")
     print("conv backward (relu; dW + db + dYpre, then dX through the transposed-weight forward convolution)")
-    for (B, Ci, Co, T, K, relu) in [(64, 512, 1024, 200, 3, 1), (64, 1024, 80, 200, 1, 0)]:
+    for (B, Ci, Co, T, K, relu) in [(64, 512, 1024, 200, 3, 1), (64, 1024, 80, 200, 1, 0), (64, 1024, 80, 200, 1, 1),
+                                    (64, 80, 160, 900, 3, 1), (64, 160, 80, 900, 1, 1), (64, 80, 80, 900, 1, 1)]:
         x = torch.randn(B, Ci, T, generator=g).to(dev)
         w = (torch.randn(Co, Ci, K, generator=g) / (Ci * K) ** 0.5).to(dev)
         bias = torch.randn(Co, generator=g).to(dev)
-        y = torch.empty(B, Co, T, device=dev)
+        y = torch.randn(B, Co, T, generator=g).to(dev).relu_()        # (the timed forward overwrites it with its own output)
         gy = torch.randn(B, Co, T, generator=g).to(dev)
         gyp, gx = torch.empty_like(gy), torch.empty_like(x)
         gw, gb = torch.empty_like(w), torch.empty_like(bias)
@@ -84,6 +89,9 @@ def main():
                                                                        B, Ci, Co, T, K, relu, st))
         bx = lambda: _lib.check(lib.aligner_conv1d_prepared_ws_f32(gyp.data_ptr(), prept.data_ptr(), None, gx.data_ptr(),  # noqa: E731
                                                                    wsb.data_ptr(), nb, B, Co, Ci, T, K, 0, st))
+        tp = ev(lambda: _lib.check(lib.aligner_conv1d_prepare_f32(w.data_ptr(), prep.data_ptr(), n, Co, Ci, K, st)), a.iters)
+        tpt = ev(lambda: _lib.check(lib.aligner_conv1d_prepare_transposed_f32(w.data_ptr(), prept.data_ptr(), nt, Co, Ci, K, st)),
+                 a.iters)
         tf = ev(fwd, a.iters)
         tw = ev(bw, a.iters)
         tx = ev(bx, a.iters)
@@ -91,7 +99,7 @@ def main():
         bytes_w = 4.0 * (B * Ci * T + 3 * B * Co * T + Co * Ci * K)
         print(f"  [{B},{Ci}->{Co},T={T},k={K},relu={relu}] forward {tf:.1f} us ({fl / tf / 1e6:.1f} TFLOP/s); "
               f"dW+db {tw:.1f} us ({fl / tw / 1e6:.1f} TFLOP/s, {bytes_w / tw / 1e6:.2f} TB/s); dX {tx:.1f} us; "
-              f"backward total {tw + tx:.1f} us = {(tw + tx) / tf:.2f}x forward")
+              f"backward total {tw + tx:.1f} us = {(tw + tx) / tf:.2f}x forward; prepare {tp:.1f} us, transposed {tpt:.1f} us")
 
 
 if __name__ == "__main__":
