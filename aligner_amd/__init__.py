@@ -29,6 +29,8 @@ from .banddtw import (band_to_dense, dense_to_band, l1_cost_banded, l1_cost_band
 from .dtwpath import DtwPath, dtw_path, dtw_path_banded, dtw_path_l1, path_to_dense  # noqa: F401
 from .l2cost import (dtw_path_l2, l2_cost, l2_cost_backward, l2_cost_banded, l2_cost_banded_backward, mcd_dtw,  # noqa: F401
                      soft_dtw_l2_banded_loss, soft_dtw_l2_loss)
+from .pathcost import (PathRuns, dtw_l1_loss, dtw_l2_loss, mcd_dtw_loss, path_cost, path_cost_backward,  # noqa: F401
+                       path_runs)
 
 __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status",
            "soft_attention", "soft_attention_backward", "conv1d", "conv1d_backward", "alignment_encoder", "AlignmentEncoderParams",
@@ -43,6 +45,7 @@ __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status"
            "dtw_path", "dtw_path_banded", "dtw_path_l1", "path_to_dense", "DtwPath",
            "l2_cost", "l2_cost_backward", "soft_dtw_l2_loss", "l2_cost_banded", "l2_cost_banded_backward",
            "soft_dtw_l2_banded_loss", "dtw_path_l2", "mcd_dtw",
+           "path_runs", "PathRuns", "path_cost", "path_cost_backward", "dtw_l1_loss", "dtw_l2_loss", "mcd_dtw_loss",
            "install_dropin"]
 
 

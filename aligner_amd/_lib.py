@@ -131,7 +131,14 @@ SIGNATURES = {
     "aligner_dtw_path_f32": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "aligner_dtw_path_banded_workspace_bytes": (_sz, [_i, _i, _i]),
     "aligner_dtw_path_banded_f32": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "aligner_path_runs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "aligner_path_cost_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "aligner_path_cost_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "aligner_path_cost_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz,
+                                            _i, _i, _i, _i, _i, _vp]),
 }
+
+COST_L1, COST_L2, COST_L2_ROOT = range(3)      # ALIGNER_COST_* (include/aligner_amd.h)
 
 
 EINVAL, EDOM, ENOSPC = -22, -33, -28     # ALIGNER_E* (include/aligner_amd.h)

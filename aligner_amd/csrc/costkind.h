@@ -13,6 +13,9 @@
 //     L2       d = t - p, acc = fma(d, d, acc)      back: d = p - t, acc = fma(G, d, acc)                       k = (2 scale) g
 //     L2Root   L2's sum, sqrt(acc) scale            no gradient (it needs the finished table and is singular at 0)
 //
+// Along a warping path only the path's own distances are needed, and there the root has a gradient too: pathcost.hip
+// runs these pieces on the pairs of a path and keeps the root's backward pieces (PathRootGrad) to itself.
+//
 // L1 and L2 are two vector instructions per cell and channel.  A masked G of +0 times a finite d is 0, so the backward
 // kernels take their pred rows and target columns from inside the utterance's lengths (a NaN in the padding past
 // n[b] or m[b] would otherwise ride in on 0 * NaN); the selection of L1 never needed that and is unchanged by it.

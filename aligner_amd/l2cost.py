@@ -14,8 +14,8 @@ is l1cost.py's and banddtw.py's, through the same helpers.
 
 The squared kind is the cost Soft-DTW was defined with; what it replaces is torch.cdist(p=2) ** 2 in front of
 soft_dtw_loss(), which builds and keeps the whole [B,N,M] table whatever the band and does not exist in band storage.
-The root kind is the distance MCD-DTW averages.  It is forward only: its gradient needs the finished table back and is
-singular at distance 0, and nothing that trains needs it.
+The root kind is the distance MCD-DTW averages.  As a table it is forward only: its gradient needs the finished table
+back and is singular at distance 0.  Along a warping path it has one (pathcost.py: mcd_dtw_loss()).
 
 The cell is the direct form, d = target - pred and acc = fma(d, d, acc) over the channels in order, in fp32 on the
 vector ALU: its error is relative to the distance itself.  (gaussian_logp with a zero log-std is also a scaled squared

@@ -52,7 +52,9 @@ extern "C" {
  *    aligner_l1_cost_banded_backward_f32; and hard DTW, the minimum-cost warping path with its backtrack, in both
  *    storage forms -- aligner_dtw_path_f32 / aligner_dtw_path_banded_f32 and their *_workspace_bytes; and the
  *    Euclidean cost tables, squared (with the gradient) and root, in both storage forms -- aligner_l2_cost_f32 /
- *    aligner_l2_cost_backward_f32 / aligner_l2_cost_banded_f32 / aligner_l2_cost_banded_backward_f32. */
+ *    aligner_l2_cost_backward_f32 / aligner_l2_cost_banded_f32 / aligner_l2_cost_banded_backward_f32; and the cost
+ *    kinds along a path, forward and backward -- aligner_path_runs / aligner_path_cost_f32 /
+ *    aligner_path_cost_backward_f32 / aligner_path_cost_backward_workspace_bytes. */
 #define ALIGNER_ABI_VERSION 5
 
 /* error codes */
@@ -961,6 +963,69 @@ int aligner_dtw_path_banded_f32(const float *cost_band_dev, const int32_t *n_dev
                                 float warp_penalty, int bandwidth,
                                 float *value_out_dev, int32_t *path_out_dev, int32_t *length_out_dev,
                                 void *ws_dev, size_t ws_bytes, int B, int N, void *hip_stream);
+
+/*
+ * The cost kinds along a path: the cells of the cost tables above evaluated on the pairs of a warping path instead of
+ * on a table, forward and backward -- what makes the hard path a loss (the gamma -> 0 limit of the soft losses) and an
+ * evaluation along the path one call for the batch, with no cost table kept.  Build-defined.
+ *   pred_dev [B,C,N], target_dev [B,C,M] fp32 contiguous, channels first; n_dev / m_dev optional [B] int32, clamped to
+ *   N / M; path_dev [B,L,2] int32 and length_dev [B] int32 as aligner_dtw_path_f32 / aligner_dtw_path_banded_f32 write
+ *   them (pairs ascending, L whatever the buffer has).  The features need not be those the path was found on.
+ *   kind: ALIGNER_COST_L1, ALIGNER_COST_L2 (squared) or ALIGNER_COST_L2_ROOT.
+ *
+ * aligner_path_cost_f32.  pair_cost[b,k], k < length[b] (a length outside [0,L] is clamped), is the cell (i_k,j_k) of
+ * aligner_l1_cost_f32 / aligner_l2_cost_f32 with the same scale, bit for bit: the same operations over the channels in
+ * order.  A pair with i outside [0,n) or j outside [0,m) costs +inf and nothing is read for it; pair_cost[b,k] = 0 for
+ * k >= length[b].  total_out_dev (optional [B]): the sum of the length[b] pair costs in a fixed order by one workgroup
+ * per utterance, +inf for a length below 1.  No atomics: the same bits on every call.
+ *
+ * aligner_path_runs.  The pairs of a warping path with row i are consecutive in k, and so are those with column j.
+ * row_start[b,i] is the index k of the first pair with row i and row_count[b,i] how many follow with that row (-1 and 0
+ * for a row not on the path); col_start / col_count [B,M] alike; all int32.  valid[b] = 1 iff 0 <= length[b] <= L,
+ * every pair k < length[b] lies in [0,N) x [0,M) and every step is (1,1), (1,0) or (0,1); an utterance that is not
+ * valid has every count 0 and every start -1, and causes no access outside a buffer.  Every element is written, by one
+ * writer.
+ *
+ * aligner_path_cost_backward_f32.  With the weights w_k = pair_weight_dev[b,k] ([B,L], null: all 1; not read at
+ * k >= length[b]), g = row_scale_dev[b] (null: 1) and d_k,c = pred[b,c,i_k] - target[b,c,j_k]:
+ *
+ *     dpred[b,c,i]   =  factor sum over the pairs k of row i's run     of  w_k s(d_k,c)
+ *     dtarget[b,c,j] = -factor sum over the pairs k of column j's run  of  w_k s(d_k,c)
+ *     L1:       s = sign(d), sign(0) = 0                      factor = scale g
+ *     L2:       s = d                                         factor = (2 scale) g
+ *     L2_ROOT:  s = d / dist_k, dist_k = sqrt(sum_c d_k,c^2) as the forward computes it, s = 0 for every channel when
+ *               dist_k == 0                                   factor = scale g
+ *
+ * The run is accumulated in k order and multiplied by the factor once.  The root kind forms the coefficient w_k / dist_k
+ * per pair first (dist_k is 0 or at least 2^-74.5: finite for |w_k| < 2^53) and then runs L2's arithmetic with it.  Pairs
+ * are read only inside [0,n) x [0,m), a pair outside contributes 0; rows, columns and utterances without pairs -- an
+ * utterance aligner_path_runs calls not valid among them -- are written exactly 0 whatever row_scale holds.  One owner
+ * per output element and no atomics: the same bits on every call, and each of dpred_out_dev [B,C,N] / dtarget_out_dev
+ * [B,C,M] (either may be null, not both) has the bits it has beside the other.  ws_dev:
+ * aligner_path_cost_backward_workspace_bytes(kind,B,N,M,L) bytes (0: outside the domain), 4-byte aligned: the runs and
+ * the root kind's coefficients.
+ *
+ * Domain: B <= 65535, C <= 4096, L < 2^24: ALIGNER_EDOM beyond; ALIGNER_EINVAL for a null pointer, a shape below 1, an
+ * unknown kind, a scale that is not finite; ALIGNER_ENOSPC for a workspace that is too small.  Validated before any HIP
+ * call.  Asynchronous on the stream, capturable.
+ */
+#define ALIGNER_COST_L1      0
+#define ALIGNER_COST_L2      1
+#define ALIGNER_COST_L2_ROOT 2
+int aligner_path_runs(const int32_t *path_dev, const int32_t *length_dev,
+                      int32_t *row_start_out_dev, int32_t *row_count_out_dev,
+                      int32_t *col_start_out_dev, int32_t *col_count_out_dev, int32_t *valid_out_dev,
+                      int B, int L, int N, int M, void *hip_stream);
+int aligner_path_cost_f32(const float *pred_dev, const float *target_dev, const int32_t *path_dev, const int32_t *length_dev,
+                          const int32_t *n_dev, const int32_t *m_dev, int kind, float scale,
+                          float *pair_cost_out_dev, float *total_out_dev,
+                          int B, int C, int N, int M, int L, void *hip_stream);
+size_t aligner_path_cost_backward_workspace_bytes(int kind, int B, int N, int M, int L);
+int aligner_path_cost_backward_f32(const float *pair_weight_dev, const float *pred_dev, const float *target_dev,
+                                   const int32_t *path_dev, const int32_t *length_dev,
+                                   const int32_t *n_dev, const int32_t *m_dev, int kind, float scale,
+                                   const float *row_scale_dev, float *dpred_out_dev, float *dtarget_out_dev,
+                                   void *ws_dev, size_t ws_bytes, int B, int C, int N, int M, int L, void *hip_stream);
 
 #ifdef __cplusplus
 }
