@@ -19,6 +19,7 @@ from .objective import (alignment_loss, average_by_duration, beta_binomial_prior
                         forward_sum_loss, regulate, segment_reduce)
 from .mobo import BoundarySearch, boundary_search, boundary_search_backward, soft_boundaries  # noqa: F401
 from .pausepath import PauseAlignment, align_with_pauses  # noqa: F401
+from .ctcalign import CtcAlignment, ctc_forced_align, ctc_token_spans  # noqa: F401
 from .gausslogp import gaussian_align, gaussian_forward_sum_loss, gaussian_logp, gaussian_logp_backward  # noqa: F401
 from .gaussnll import gaussian_nll, gaussian_nll_loss  # noqa: F401
 from .gaussup import gaussian_upsample, gaussian_upsample_at  # noqa: F401
@@ -36,7 +37,7 @@ __all__ = ["Alignment", "align", "maximum_path", "maximum_path_c", "read_status"
            "soft_attention", "soft_attention_backward", "conv1d", "conv1d_backward", "alignment_encoder", "AlignmentEncoderParams",
            "forward_sum", "forward_sum_loss", "beta_binomial_prior", "regulate", "segment_reduce", "average_by_duration", "binarization_loss", "alignment_loss",
            "boundary_search", "boundary_search_backward", "soft_boundaries", "BoundarySearch",
-           "align_with_pauses", "PauseAlignment", "gaussian_logp", "gaussian_logp_backward", "gaussian_forward_sum_loss",
+           "align_with_pauses", "PauseAlignment", "ctc_forced_align", "ctc_token_spans", "CtcAlignment", "gaussian_logp", "gaussian_logp_backward", "gaussian_forward_sum_loss",
            "gaussian_align", "gaussian_nll", "gaussian_nll_loss",
            "gaussian_upsample", "gaussian_upsample_at", "soft_dtw", "soft_dtw_loss",
            "l1_cost", "l1_cost_backward", "soft_dtw_l1_loss",

@@ -104,6 +104,9 @@ SIGNATURES = {
     "aligner_bin_loss_grad_f32": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
     "aligner_pausepath_workspace_bytes": (_sz, [_i, _i, _i]),
     "aligner_pausepath": (_i, [_vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "aligner_ctc_align_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aligner_ctc_align": (_i, [_vp, _i, _c.c_longlong, _c.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _sz, _i, _i, _i, _vp]),
     "aligner_gauss_logp_workspace_bytes": (_sz, [_i, _i, _i]),
     "aligner_gauss_logp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
     "aligner_gauss_logp_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),

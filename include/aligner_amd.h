@@ -720,6 +720,52 @@ int aligner_pausepath(const void *value_dev, int value_dtype, int ld_value, cons
                       void *workspace_dev, size_t workspace_bytes, int B, int Tx, int Ty, void *stream);
 
 /*
+ * CTC forced alignment from emissions: the Viterbi path of a transcript through the frame scores of a CTC acoustic
+ * model (what torchaudio.functional.forced_align computes, for a whole batch and with repeated labels; build-defined
+ * spec, stated in full in csrc/ctcalign.hip and tests/ctcalign_oracle.py).  Per utterance b: t_y = t_ys[b] frames,
+ * t_x = t_xs[b] labels lab[x] = targets[b,x], emissions e[y,v] = log_probs[b,y,v] -- any scores, they need not be
+ * normalised; read as fp32, 16-bit inputs up-cast exactly.
+ * States s = 0 .. 2 t_x: s = 2g is the blank in gap g (the place before token g; gap 0 leads, gap t_x trails) and scores
+ * e[y,blank]; s = 2x+1 is token x and scores e[y,lab[x]].  Moves: stay s -> s, advance s-1 -> s, and skip s-2 -> s only
+ * into a token x >= 1 with lab[x] != lab[x-1]: between two equal labels the blank is mandatory.  A token takes at
+ * least one frame, a blank zero or more.
+ * Band: a state exists at frame y iff it lies on a legal path.  With r[x] = 1 if x >= 1 and lab[x] == lab[x-1] else 0,
+ * R[x] = r[0] + .. + r[x] and Rt = R[t_x-1]:
+ *   token x iff x + R[x] <= y and t_y-1-y >= (t_x-1-x) + (Rt - R[x]);
+ *   blank g iff g + (g >= 1 ? R[g-1] : 0) <= y and t_y-1-y >= (t_x-g) + (g < t_x ? Rt - R[g] : 0).
+ * Recurrence, ties and end are aligner_pausepath's: Q[s,0] = score(s,0) for the states 0 and 1 that exist;
+ * Q[s,y] = Q[pred,y-1] + score(s,y), one fp32 add; pred among the candidates that exist at y-1 in the order stay,
+ * advance, skip, a later one replacing an earlier one only when strictly greater (a NaN never wins); the path ends in
+ * 2 t_x - 1 unless the trailing blank exists at t_y-1 and is strictly greater.  Absent candidates are excluded, not
+ * scored: the result is a legal path for any scores, -inf and NaN included.
+ *   log_probs_dev [B,T,V] of dtype F32, BF16 or F16; stride_b, stride_t in elements, the vocabulary axis contiguous
+ *                 (stride_t >= V; any stride_b >= 0: a [T,B,V] tensor is read in place with stride_b = V, stride_t = B V)
+ *   blank in [0,V).  A label equal to blank is an ordinary label that happens to score the blank column.
+ *   targets_dev [B,L] int32; t_xs_dev (target lengths), t_ys_dev (input lengths) [B] int32
+ * Outputs, each optional, at least one; every element of a requested one is written:
+ *   tok_out [B,T] int32: x on a frame of token x, -2-g on a blank frame of gap g, -1 for y >= t_y (aligner_pausepath's)
+ *   labels_out [B,T] int32: the vocabulary entry of the frame's state, lab[x] or blank; -1 for y >= t_y
+ *   frame_scores_out [B,T] fp32: the emission at that state (the input's bits, up-cast); 0 for y >= t_y
+ *   durations_out [B,L], pauses_out [B,L+1], state_durations_out [B,2L+1] int32, score_out [B] fp32: as aligner_pausepath's
+ * No path: t_x < 1, t_y < 1, t_x + Rt > t_y, a length outside [0,L] / [0,T], or a label outside [0,V) (checked as the
+ * labels are loaded, before any emission is read: no load leaves a row of V).  Such an utterance gets durations and
+ * pauses 0, tok and labels -1, frame_scores 0 and score -inf; the others of the batch are unaffected.
+ * One launch, one workgroup per utterance, no atomics: deterministic.  ALIGNER_EINVAL: a null input, no output, a bad
+ * shape (B < 0, L < 1 or T < 1; B = 0 is an empty batch and succeeds), V < 1, blank outside [0,V), stride_t < V,
+ * stride_b < 0, a dtype other than the three.  ALIGNER_EDOM: L > 1024, B > 65535,
+ * (T-1)*stride_t + V or the number of decision words beyond 2^31.  The workspace holds decision words only, for shapes
+ * whose words do not fit LDS: aligner_ctc_align_workspace_bytes(B,L,T) bytes, 0 when they fit and 0 for an unsupported
+ * shape, decided against gfx950's 160 KiB as aligner_pausepath_workspace_bytes does; ALIGNER_ENOSPC for a short one.
+ */
+size_t aligner_ctc_align_workspace_bytes(int B, int L, int T);
+int aligner_ctc_align(const void *log_probs_dev, int dtype, long long stride_b, long long stride_t, int V, int blank,
+                      const int32_t *targets_dev, const int32_t *t_xs_dev, const int32_t *t_ys_dev,
+                      int32_t *tok_out_dev, int32_t *labels_out_dev, float *frame_scores_out_dev,
+                      int32_t *durations_out_dev, int32_t *pauses_out_dev, int32_t *state_durations_out_dev,
+                      float *score_out_dev, void *workspace_dev, size_t workspace_bytes, int B, int L, int T,
+                      void *stream);
+
+/*
  * MoBoAligner monotonic boundary search (BASELINE config 5; build-defined spec from the paper the reference
  * links at README.md:49 -- its code is on a branch that is not in the snapshot; stated in full in
  * oracle/mobo_oracle.py and aligner_amd/csrc/mobo.hip).  Boundaries 0 = b_-1 < b_0 < ... < b_{t_x-1} = t_y,
