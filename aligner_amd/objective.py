@@ -126,6 +126,8 @@ def beta_binomial_prior(t_x: torch.Tensor, t_y: torch.Tensor, T_text: int, T_mel
     tx = _lengths(t_x, B, dev, "t_x")
     ty = _lengths(t_y, B, dev, "t_y")
     out = torch.empty((B, T_text, T_mel), dtype=torch.float32, device=dev)
+    if B == 0:
+        return out                                       # (an empty tensor has a null pointer, which the C ABI rejects)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().aligner_beta_binomial_prior_f32(tx.data_ptr(), ty.data_ptr(), out.data_ptr(), B, T_text,
                                                                T_mel, float(scaling), stream(dev)))

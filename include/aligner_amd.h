@@ -624,7 +624,10 @@ int aligner_forward_sum_ctc_f32(const float *scores_dev, const int32_t *t_xs_dev
                                 int B, int Tx, int Ty, void *stream);
 
 /* prior[b,x,y] = BetaBinomial(n = t_x, a = scaling*(y+1), b = scaling*(t_y-y)).pmf(x) for x < t_x,
- * y < t_y, 0 elsewhere; [B,Tx,Ty] fp32, the `prior_dev` operand of aligner_softattn_f32. */
+ * y < t_y, 0 elsewhere; [B,Tx,Ty] fp32, the `prior_dev` operand of aligner_softattn_f32.
+ * t_x = t_xs[b] clamped to [0,Tx] and t_y = t_ys[b] clamped to [0,Ty]: a longer utterance gets the prior of the
+ * container's extent, one with t_x < 1 is all zero.  `scaling` is used at its fp32 value.  Tx <= 7679 (ALIGNER_EDOM
+ * beyond); scaling <= 0 or NaN is ALIGNER_EINVAL. */
 int aligner_beta_binomial_prior_f32(const int32_t *t_xs_dev, const int32_t *t_ys_dev, float *prior_out_dev,
                                     int B, int Tx, int Ty, float scaling, void *stream);
 
